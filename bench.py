@@ -1,6 +1,6 @@
 """bench.py -- throughput of the MVIP-NeRF hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch of synthetic input: one 378x504 frame
 (190,512 rays), coarse 64 + fine 128 samples, test-mode kwargs.
@@ -10,17 +10,23 @@ One "step" = one pass of the hot path over one batch of synthetic input (SURVEY.
          maps on every rank), `scaling: "strong"`; a scaling curve that CAN fail.  Beside it: `weak_rays_per_sec` (every
          rank renders its own whole frames, no collective: N x by construction), `value_1_same_run` (one rank's
          whole-frame rate from that weak leg) and `strong_efficiency = value / (N * value_1_same_run)`.
-Further legs in the same JSON line: the
+A plain run measures only that headline: set-up, W warm-up steps, K timed steps, one JSON line (`ms_per_step` = wall
+time of one timed step).  `--dump-outputs DIR` writes what the last timed step returned (render()'s maps and extras,
+or render_sharded()'s maps at N > 1) as DIR/<name>.npy in float32; the inputs (seeded weights, fixed orbit poses) are
+the same in every run with the same arguments, so two builds can be compared output for output (see dump_outputs).
+`--full` adds everything else to the same JSON line: at N > 1 the weak-scaling and one-rank legs, the roofline of the
+dominant kernel, the
 second-stage training iteration (rays sharded, ONE 4.77 MB gradient all-reduce), the SDS step with its own roofline
 (FLOPs counted from the layer shapes), the full BASELINE configs[1]/[2]/[3] iterations (SDS terms owned by different
-ranks), and the CPU baseline (oracle on the host cores: render, train and SDS legs, >= 3 warm-ups, median of >= 5).
+ranks), the split-precision and hash-grid legs, the scaling prediction, and the CPU baseline (oracle on the host cores:
+render, train and SDS legs, >= 3 warm-ups, median of >= 5).
 
 Launch: with N > 1 and no WORLD_SIZE in the environment this process only SPAWNS the N ranks
 (`python -m torch.distributed.run --nproc-per-node N ... bench.py`, rendezvous on 127.0.0.1) before touching any
 GPU, relays rank 0's JSON line and exits with the children's status; under an external launcher (WORLD_SIZE set)
 --gpus must equal the world size.  Rank 0 prints ONE JSON line.
 
-Exit status: 0 only if every leg ran.  The legs after the headline measurement exercise the collectives (sharded
+Exit status: 0 only if every leg ran.  The legs after the headline measurement (--full) exercise the collectives (sharded
 training iteration, view-sharded SDS terms, the gradient all-reduce); they run under a watchdog whose deadline lies well
 below the RCCL timeout.  If one of them raises or the deadline passes, rank 0 still prints the line -- with what was
 measured so far and an `extra_legs_error` -- and every rank leaves with status 3 (a plain exit of the rank process).
@@ -63,6 +69,48 @@ def orbit_pose(k, device):
     c, s = math.cos(th), math.sin(th)
     return torch.tensor([[c, 0., s, 0.3 * s], [0., 1., 0., 0.], [-s, 0., c, 0.3 * c]], dtype=torch.float32,
                         device=device)
+
+
+RENDER_OUTPUTS = ('rgb_map', 'disp_map', 'acc_map', 'depth_map')
+DUMP_MAX_BYTES = 64 << 20
+DUMP_WHOLE_MAX_BYTES = 4 << 20         # arrays above this (the per-sample weights / z_vals) are dumped on a ray sample
+DUMP_SAMPLE_RAYS = 8192
+
+
+def dump_outputs(out, dirname, seed=0):
+    """Write a render step's outputs ([rgb, disp, acc, depth] + an extras dict, as render() / render_sharded() return
+    them) as dirname/<name>.npy, float32.  Arrays of at most DUMP_WHOLE_MAX_BYTES are written whole; larger ones
+    ([H, W, samples]) are written on a fixed sample of DUMP_SAMPLE_RAYS rays (drawn with `seed`, sorted), whose flat
+    ray indices go to sample_ray_index.npy (float64).  At most DUMP_MAX_BYTES in all.
+    Every written value is finite.  Where an output holds non-finite values -- disp = 1 / max(1e-10, depth / acc) is NaN
+    on rays whose weights are all zero (0 / 0, as in the reference) -- they are written as 0 and <name>_nonfinite.npy
+    (float32, same shape) marks them: 1 = NaN, 2 = +inf, 3 = -inf, 0 = finite."""
+    named = dict(zip(RENDER_OUTPUTS, out[:4]))
+    if len(out) > 4:
+        named.update(out[4])
+    os.makedirs(dirname, exist_ok=True)
+    n_rays = named['rgb_map'].shape[0] * named['rgb_map'].shape[1]
+    sel = np.sort(np.random.default_rng(seed).choice(n_rays, min(DUMP_SAMPLE_RAYS, n_rays), replace=False))
+    sel_dev = None
+    arrays = {}
+    for name in sorted(named):
+        t = named[name].detach()
+        if t.element_size() * t.numel() > DUMP_WHOLE_MAX_BYTES:
+            if sel_dev is None:
+                sel_dev = torch.from_numpy(sel).to(t.device)
+                arrays['sample_ray_index'] = sel.astype(np.float64)
+            t = t.reshape(n_rays, -1).index_select(0, sel_dev)
+        a = t.float().cpu().numpy()
+        bad = ~np.isfinite(a)
+        if bad.any():
+            arrays[name + '_nonfinite'] = np.where(np.isnan(a), 1, np.where(a > 0, 2, 3)).astype(np.float32) * bad
+            a = np.where(bad, np.float32(0), a)
+        arrays[name] = a
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f'dump of {total} bytes exceeds {DUMP_MAX_BYTES}'
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + '.npy'), a)
+    return sorted(arrays)
 
 
 def _median_time(fn, warmup, reps):
@@ -362,7 +410,8 @@ def add_scaling_prediction(result, world):
 
 
 def dry_run(world, rank, args):
-    """MVIP_BENCH_DRYRUN=1: the launch / rendezvous / watchdog path without GPU work (CPU tests of the launcher).
+    """MVIP_BENCH_DRYRUN=1: the launch / rendezvous / watchdog path without GPU work (CPU tests of the launcher); the
+    weak-scaling field and the extra leg under the watchdog only with --full, as in a real run.
     MVIP_BENCH_DRYRUN_HANG_RANK=r makes rank r sleep instead of joining the extra leg's collective."""
     import torch.distributed as dist
     result = {}
@@ -390,9 +439,11 @@ def dry_run(world, rank, args):
     assert torch.equal(maps[0], torch.stack([v, v + 1, v + 2], -1).reshape(Hd, Wd, 3)) and torch.equal(maps[3], (v * 4).reshape(Hd, Wd))
     result.update({'metric': 'dry-run (launcher only)', 'value': 0.0, 'unit': 'rays/s', 'n_gpus': world,
               'steps': args.steps, 'warmup': args.warmup, 'scaling': 'strong' if world > 1 else 'weak',
-              'weak_rays_per_sec': 0.0, 'strong_efficiency': None, 'sharded_frame_assembled': True,
+              'sharded_frame_assembled': True,
               'multi_gpu': {'rccl_world': dist.get_world_size() if world > 1 else 1,
                             'backend': dist.get_backend() if world > 1 else None}})
+    if args.full:
+        result.update({'weak_rays_per_sec': 0.0, 'strong_efficiency': None})
 
     def extra():
         if os.environ.get('MVIP_BENCH_DRYRUN_HANG_RANK') == str(rank):
@@ -403,7 +454,7 @@ def dry_run(world, rank, args):
             t = torch.tensor([1.0])
             dist.all_reduce(t)
         result['extra_leg'] = 'done'
-    rep.guarded(extra)
+    rep.guarded(extra if args.full else (lambda: None))
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
@@ -420,7 +471,14 @@ def main():
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--cpu-warmup', type=int, default=3)
     ap.add_argument('--cpu-reps', type=int, default=5)
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32; see dump_outputs)")
+    ap.add_argument('--full', action='store_true',
+                    help='also run every leg besides the headline: weak / one-rank legs at N > 1, roofline, training, '
+                         'SDS, configs[2] / configs[3], split precision, hash grid, scaling prediction, CPU baseline')
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit('bench.py: --steps must be at least 1')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         raise SystemExit(spawn_ranks(args.gpus, sys.argv[1:]))
@@ -458,14 +516,13 @@ def main():
 
     def step(k):                                    # one WHOLE frame on this rank (N = 1 headline; the weak leg at N > 1)
         with torch.no_grad():
-            out = run.render(H, W, FOCAL, chunk=1 << 15, c2w=orbit_pose(k * world + rank, device), near=NEAR,
-                             far=FAR, **te)
-        return out[0]
+            return run.render(H, W, FOCAL, chunk=1 << 15, c2w=orbit_pose(k * world + rank, device), near=NEAR,
+                              far=FAR, **te)
 
     def step_strong(k):                             # ONE frame over all ranks: rays in contiguous blocks, maps all-gathered
         with torch.no_grad():
             return run.render_sharded(H, W, FOCAL, orbit_pose(k, device), rank, world, dist, chunk=1 << 15, near=NEAR,
-                                      far=FAR, **te)[0]
+                                      far=FAR, **te)
 
     def barrier():
         if dist is not None:
@@ -473,32 +530,42 @@ def main():
         torch.cuda.synchronize()
 
     def timed(fn):
-        """W untimed warm-up steps, then exactly K steps between barrier + synchronize; max over ranks."""
+        """W untimed warm-up steps, then exactly K steps between barrier + synchronize; max over ranks.
+        Returns (seconds, what the last timed step returned)."""
         for k in range(args.warmup):
             fn(k)
         barrier()
         t0 = time.perf_counter()
         for k in range(args.steps):
-            fn(args.warmup + k)
+            last = None                              # the previous step's outputs are freed before the next one, as in warm-up
+            last = fn(args.warmup + k)
         barrier()
         dt_ = time.perf_counter() - t0
         if dist is not None:
             t = torch.tensor([dt_], device=device, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt_ = float(t.item())
-        return dt_
+        return dt_, last
 
     rays_per_step = H * W * world                    # of the weak form (one frame per rank)
     workload = ('render 378x504 frame, 64 coarse + 128 fine samples, 8x256 MLP x2, lindisp, '
                 'white_bkgd, test-mode kwargs (BASELINE configs[1] geometry at the metric resolution)')
+    extra = {}
     if world == 1:
-        dt = timed(step)
-        value, scaling, extra = H * W * args.steps / dt, 'weak', {}
+        dt, last_out = timed(step)
+        value, scaling = H * W * args.steps / dt, 'weak'
         par = 'rays x1 (whole frames on one GPU)'
     else:
-        dt_weak = timed(step)                        # every rank its own frames, no collective: N x by construction
-        dt = timed(step_strong)                      # the headline at N > 1: fixed work, one frame over all ranks
+        if args.full:
+            dt_weak, _ = timed(step)                 # every rank its own frames, no collective: N x by construction
+        dt, last_out = timed(step_strong)            # the headline at N > 1: fixed work, one frame over all ranks
         value, scaling = H * W * args.steps / dt, 'strong'
+        par = (f'one frame over {world} ranks: contiguous ray blocks of {-(-H * W // world)} rays, one all_gather of the maps '
+               f'per frame ({"RCCL over xGMI" if backend == "nccl" else backend})')
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last_out, args.dump_outputs)
+    del last_out
+    if world > 1 and args.full:
         # The one-GPU baseline of this same run, measured with the OTHER ranks idle (they wait at the barrier): rank 0 renders
         # whole frames alone, so neither a shared device nor contention for host / fabric halves it (ADVICE r4).
         for k in range(args.warmup):
@@ -524,8 +591,6 @@ def main():
                  'strong_what': 'each frame cut into N contiguous ray blocks (run.render_sharded), ONE all_gather of '
                                 f'[{H * W}, 6] fp32 = {H * W * 24 / 1e6:.2f} MB per frame so every rank holds rgb / disp / acc / depth; '
                                 'value_1_same_run = whole frames on rank 0 ALONE (the other ranks idle at a barrier)'}
-        par = (f'one frame over {world} ranks: contiguous ray blocks of {-(-H * W // world)} rays, one all_gather of the maps '
-               f'per frame ({"RCCL over xGMI" if backend == "nccl" else backend})')
     result.update({
         'metric': 'rays_per_sec (coarse+fine, 64+128 samples, 504x378)', 'value': value,
         'unit': 'rays/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
@@ -539,13 +604,14 @@ def main():
     mg = {'rccl_world': dist.get_world_size() if dist is not None else 1,
           'backend': dist.get_backend() if dist is not None else None}
     result['multi_gpu'] = mg
-    if rank == 0:
+    if rank == 0 and args.full:
         result['roofline'] = kernel_roofline(run, te, device)          # local to rank 0: no collective
 
     def add_cpu_baseline(res):
         if world == 1 and not args.no_cpu_baseline:
             res['cpu_baseline'] = cpu_baseline(args.cpu_warmup, args.cpu_reps)
-    rep.before_print = add_cpu_baseline
+    if args.full:
+        rep.before_print = add_cpu_baseline
 
     def extra_legs():
         # ---- the gradient bucket's all-reduce ALONE (1,191,688 floats = 4.77 MB, the only per-iteration data-path
@@ -607,10 +673,10 @@ def main():
         # ---- extra leg: the same frames with the split-precision forward (precision = 1, "f16x3": fp16 MFMA on
         #      hi/lo splits of both operands, fp32 accumulate).  Reported separately; `value` stays exact fp32. ----
         with torch.no_grad():
-            ref_img = step(0)
+            ref_img = step(0)[0]
             for net in (te['network_fn'], te['network_fine']):
                 net.inference_precision = 1
-            fast_img = step(0)
+            fast_img = step(0)[0]
             barrier()
             tf = time.perf_counter()
             for k in range(args.steps):
@@ -926,7 +992,7 @@ def main():
         extra_legs()
         add_scaling_prediction(result, world)
 
-    rep.guarded(legs_and_prediction)
+    rep.guarded(legs_and_prediction if args.full else (lambda: None))
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()

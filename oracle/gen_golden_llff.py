@@ -71,8 +71,33 @@ def main():
     msk8 = np.stack([(down2(masks[v]) > 0.5) for v in views8])
     np.savez_compressed(os.path.join(OUT, 'scene1_f8.npz'), images=(img8 * 255 + .5).astype(np.uint8), masks=msk8,
                         poses=poses[views8], bds=bds, views=np.array(views8), factor=8, held_out_view=30)
-    for f in ('llff_scene1_f4.npz', 'scene1_small.npz', 'scene1_f8.npz'):
+    write_scene_source()
+    for f in ('llff_scene1_f4.npz', 'scene1_small.npz', 'scene1_f8.npz', 'llff_scene1_f4_src.npz'):
         print(f, os.path.getsize(os.path.join(OUT, f)) / 1024, 'KB')
+
+
+def write_scene_source():
+    """tests/golden/llff_scene1_f4_src.npz: what tests/test_host_cpu.py needs to rebuild a stand-in of scene 1's factor-4
+    folder without the 224 MB of rasters: the real poses_bounds.npy, the real file names (their sorted order is the view
+    order), and per view the exact integer sums the loader's outputs are compared on (RGB bytes, label pixels, first depth
+    channel) plus the label maximum.  The stand-in rasters carry these sums and the golden pixels of llff_scene1_f4.npz."""
+    from PIL import Image
+    root = os.path.join(DATA, 'images_4')
+    names = sorted(f for f in os.listdir(os.path.join(root, 'RGB_inpainted')) if f.endswith('.png'))
+    rgb_sum, label_sum, label_max, depth_sum = [], [], [], []
+    for f in names:
+        rgb = np.asarray(Image.open(os.path.join(root, 'RGB_inpainted', f)))[..., :3]
+        lab = np.asarray(Image.open(os.path.join(root, 'label', f)))
+        dep = np.asarray(Image.open(os.path.join(root, 'Depth_inpainted', f)))
+        lab = lab[..., 0] if lab.ndim > 2 else lab
+        dep = dep[..., 0] if dep.ndim > 2 else dep
+        rgb_sum.append(int(rgb.astype(np.int64).sum()))
+        label_sum.append(int(lab.astype(np.int64).sum()))
+        label_max.append(int(lab.max()))
+        depth_sum.append(int(dep.astype(np.int64).sum()))
+    np.savez_compressed(os.path.join(OUT, 'llff_scene1_f4_src.npz'), poses_bounds=np.load(os.path.join(DATA, 'poses_bounds.npy')),
+                        names=np.array(names), shape=np.array(rgb.shape), rgb_sum=np.array(rgb_sum), label_sum=np.array(label_sum),
+                        label_max=np.array(label_max), depth_sum=np.array(depth_sum))
 
 
 if __name__ == '__main__':

@@ -327,7 +327,7 @@ def test_sharded_frame_render_general_row_assembly(cuda):
 
 @pytest.mark.slow
 def test_bench_two_ranks_on_one_device_reports_strong_scaling(cuda):
-    """`bench.py --gpus 2` end to end on the GPU box: it starts its own two ranks (both on GPU 0 over gloo,
+    """`bench.py --gpus 2 --full` end to end on the GPU box: it starts its own two ranks (both on GPU 0 over gloo,
     MVIP_BENCH_SINGLE_DEVICE=1 -- the boxes have one GPU), renders the frame in two ray blocks joined by one all_gather, runs
     the sharded training legs, and prints ONE line whose `value` is the strong-scaling figure with the weak one beside it."""
     import json
@@ -337,7 +337,7 @@ def test_bench_two_ranks_on_one_device_reports_strong_scaling(cuda):
     env = dict(os.environ, MVIP_BENCH_SINGLE_DEVICE='1', MVIP_GRAPHS_WITH_DIST='1', MASTER_ADDR='127.0.0.1')
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_PORT'):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '1', '--warmup', '1', '--train-steps', '1',
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '1', '--warmup', '1', '--full', '--train-steps', '1',
                         '--sds-steps', '1', '--no-hashgrid', '--no-cpu-baseline'], cwd=root, env=env, capture_output=True, text=True,
                        timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
