@@ -285,6 +285,30 @@ int mvip_sds_grad_dev(const float *eps_uncond, const float *eps_cond, const floa
                       void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The 2D inpainting sampler of the prior (StableDiffusion.produce_latents / decode_latents / prompt_to_img,
+ * DS_NeRF/guidance/sd_utils.py:602-666, and the inpaint preview built on the SDS step's conditioning).
+ *
+ * Decoder head: conv_norm_out -> SiLU -> conv_out of AutoencoderKL's decoder plus decode_latents' post-processing
+ * (DS_NeRF/guidance/sd_utils.py:624-631) in one launch:
+ *   img[n,o,y,x] = clamp((conv3x3(silu(gamma[c] (x - mean[n,g]) rstd[n,g] + beta[c]), weight)[o] + bias[o]) / 2 + 0.5, 0, 1)
+ * x [N, C, H, W] (dtype 0 = fp32, 1 = fp16 storage), mean / rstd [N, G] from mvip_groupnorm_stats, gamma / beta [C],
+ * weight [3, C, 3, 3], bias [3]; stride 1, zero padding 1 of the ACTIVATED input.  img [N, 3, H, W] fp32; img_u8
+ * (nullable) [N, H, W, 3] = rint(255 img), round half to even (prompt_to_img's `.round()`).  prec 0 / 2: fp32 products;
+ * 1: the reference's --fp16 mode (activations and weights rounded to fp16, fp32 sums).  C % 32 == 0, C % G == 0,
+ * any H, W >= 1 (H * W <= 2^27). */
+int mvip_vae_decoder_head(const void *x, const float *mean, const float *rstd, const float *gamma, const float *beta,
+                          const float *weight, const float *bias, int64_t N, int64_t C, int64_t H, int64_t W, int G,
+                          int dtype, float *img, uint8_t *img_u8, int prec, void *stream);
+/* One DDIM update, eta = 0 (the scheduler.step of produce_latents, DS_NeRF/guidance/sd_utils.py:617-620), with the
+ * classifier-free guidance in front of it (:613-614).  eps [2, 4, hw] = (uncond, cond) when cfg, else [1, 4, hw];
+ * x [1, 4, hw] updated in place; scal (device) = {g, sqrt(abar_t), sqrt(1 - abar_t), sqrt(abar_prev), sqrt(1 - abar_prev),
+ * t_next}:  e = e_u + g (e_c - e_u);  x <- sqrt(abar_prev) (x - sqrt(1 - abar_t) e) / sqrt(abar_t) + sqrt(1 - abar_prev) e.
+ * unet_in (nullable) [1 + cfg, in_ch, hw]: channels 0..3 of every batch entry receive the new x (the next UNet input,
+ * whose mask / masked-image channels the caller wrote once); t_out (nullable): one float, receives t_next. */
+int mvip_ddim_cfg_step(const float *eps, int cfg, const float *scal, float *x, int64_t hw, float *unet_in,
+                       int64_t in_ch, float *t_out, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * a14-a16  bilinear resize, align_corners = False: F.interpolate(pred_rgb, (512, 512), mode='bilinear') in front of
  * vae.encode (DS_NeRF/guidance/sd_utils.py:282-284, :449-452) and its adjoint.  x [planes, H, W] -> y [planes, OH, OW]
  * with torch's source-index convention (scale = in/out, src = scale*(dst+0.5)-0.5 clamped at 0); the backward gathers

@@ -74,6 +74,9 @@ _SIGNATURES = {
     'mvip_vae_sample': (_int, [_c_f, _c_f, _flt, _i64, _i64, _i64, _c_f, _c_f]),
     'mvip_vae_sample_backward': (_int, [_c_f, _c_f, _c_f, _flt, _i64, _i64, _i64, _c_f, _c_f]),
     'mvip_timestep_sincos': (_int, [_c_f, _c_f, _i64, _i64, _c_f, _c_f]),
+    'mvip_vae_decoder_head': (_int, [_c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _i64, _i64, _i64, _i64, _int, _int, _c_f, _c_f,
+                                     _int, _c_f]),
+    'mvip_ddim_cfg_step': (_int, [_c_f, _int, _c_f, _c_f, _i64, _c_f, _i64, _c_f, _c_f]),
     'mvip_resize_bilinear': (_int, [_c_f, _i64, _i64, _i64, _i64, _i64, _c_f, _c_f]),
     'mvip_resize_bilinear_backward': (_int, [_c_f, _i64, _i64, _i64, _i64, _i64, _c_f, _c_f]),
     'mvip_groupnorm_workspace_bytes': (_i64, [_i64, _i64, _i64]),

@@ -446,14 +446,28 @@ class Decoder(nn.Module):
         self.conv_norm_out = GroupNorm(32, c, eps=1e-6)
         self.conv_out = nn.Conv2d(c, 3, 3, padding=1)
 
-    def forward(self, z):
-        x = self.mid_block(self.conv_in(z))
+    def _body(self, z):
+        x = self.mid_block(conv_any(self.conv_in, z))
         for blk in self.up_blocks:
             for r in blk.resnets:
                 x = r(x)
             if blk.upsamplers is not None:
                 x = blk.upsamplers[0](x)
-        return self.conv_out(self.conv_norm_out(x, silu=True))
+        return x
+
+    def forward(self, z):
+        return conv_any(self.conv_out, self.conv_norm_out(self._body(z), silu=True))
+
+    def image(self, z, uint8=False):
+        """clamp(forward(z) / 2 + 0.5, 0, 1) -- decode_latents' post-processing (DS_NeRF/guidance/sd_utils.py:628-629) -- and,
+        when `uint8`, rint(255 image) as [N, H, W, 3].  On the device the tail (conv_norm_out -> SiLU -> conv_out -> the
+        post-processing) is ONE launch (ops.vae_decoder_head); host tensors take the torch ops (the CPU reference)."""
+        x = self._body(z)
+        if x.is_cuda:
+            from .. import ops
+            return ops.vae_decoder_head(x, self.conv_norm_out, self.conv_out, uint8)
+        img = (self.conv_out(self.conv_norm_out(x, silu=True)) / 2 + 0.5).clamp(0, 1)
+        return img, ((img * 255).round().to(torch.uint8).permute(0, 2, 3, 1).contiguous() if uint8 else None)
 
 
 class LatentDist:
@@ -534,7 +548,22 @@ class AutoencoderKL(nn.Module):
         return _EncOut(LatentDist(conv_any(self.quant_conv, self.encoder(x))))
 
     def decode(self, z, return_dict=False):
+        if z.is_cuda:
+            from .. import ops
+            with ops.precision(self.mfma_prec):
+                z = z.to(self.post_quant_conv.weight.dtype)
+                return (self.decoder(conv_any(self.post_quant_conv, z)),)
         return (self.decoder(self.post_quant_conv(z)),)
+
+    def decode_image(self, z, uint8=False):
+        """(clamp(decode(z) / 2 + 0.5, 0, 1), rint(255 .) as uint8 [N, H, W, 3] or None): the decoder's tail and the
+        post-processing in one launch on the device (Decoder.image)."""
+        if z.is_cuda:
+            from .. import ops
+            with ops.precision(self.mfma_prec):
+                z = z.to(self.post_quant_conv.weight.dtype)
+                return self.decoder.image(conv_any(self.post_quant_conv, z), uint8)
+        return self.decoder.image(self.post_quant_conv(z), uint8)
 
 
 # ---------------------------------------------------------------------------------------------- CLIP text

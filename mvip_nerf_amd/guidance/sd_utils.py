@@ -323,6 +323,118 @@ class _GraphedStep:
         return out
 
 
+def ddim_timesteps(num_inference_steps, num_train_timesteps=1000, steps_offset=1):
+    """DDIMScheduler.set_timesteps with the SD-1.x settings ("leading" spacing, steps_offset 1): step_ratio = 1000 // n,
+    timesteps = arange(n) * step_ratio reversed, + 1.  Returns (timesteps as ints, step_ratio)."""
+    n = int(num_inference_steps)
+    if n < 1 or n > num_train_timesteps:
+        raise ValueError(f'num_inference_steps must lie in [1, {num_train_timesteps}], got {num_inference_steps}')
+    step_ratio = num_train_timesteps // n
+    return [k * step_ratio + steps_offset for k in reversed(range(n))], step_ratio
+
+
+def get_timesteps(timesteps, num_inference_steps, strength):
+    """pipeline_sd_inpainting.get_timesteps (DS_NeRF/guidance/pipeline_sd_inpainting.py:751-758): the last
+    int(n * strength) timesteps and their count.  (The reference's pipeline call doubles `strength`, :978; this does not.)"""
+    init_timestep = min(int(num_inference_steps * strength), num_inference_steps)
+    t_start = max(num_inference_steps - init_timestep, 0)
+    return list(timesteps[t_start:]), num_inference_steps - t_start
+
+
+def ddim_step_scalars(alphas_host, t, step_ratio, guidance_scale, t_next=0):
+    """The scalar block of one DDIM update (eta = 0, set_alpha_to_one False: abar_prev = abar[0] below t = 0):
+    (g, sqrt(abar_t), sqrt(1 - abar_t), sqrt(abar_prev), sqrt(1 - abar_prev), t_next)."""
+    a_t = alphas_host[t]
+    prev = t - step_ratio
+    a_p = alphas_host[prev] if prev >= 0 else alphas_host[0]
+    return (float(guidance_scale), a_t ** 0.5, (1.0 - a_t) ** 0.5, a_p ** 0.5, (1.0 - a_p) ** 0.5, float(t_next))
+
+
+def _check_strength(strength):
+    if not (isinstance(strength, (int, float)) and 0.0 < float(strength) <= 1.0):
+        raise ValueError(f'strength must lie in (0, 1], got {strength!r}')
+
+
+class _SamplerStep:
+    """One denoising step of the 2D sampler -- the UNet's CFG forward on the static input buffer `unet_in`, then
+    ops.ddim_cfg_step, which updates the latents `x` in place, writes them into unet_in's latent channels and the next
+    timestep into the UNet's timestep word `tbuf` -- on static buffers, so that it can be captured once as a hipGraph
+    and replayed n times (only the scalar block `scal` is refilled between replays).  Capture follows _GraphedStep: warm-up
+    on the process's capture stream, this graph's own scratch words (ops.ZERO_SCOPE), the prompt's cached key / value
+    planes pinned; a _NoiseFeed checks that the step draws nothing."""
+
+    def __init__(self, sd, emb, cfg, latent_hw, in_ch, graph):
+        self.sd, self.emb, self.cfg = sd, emb, cfg
+        dev = sd.device
+        B = 2 if cfg else 1
+        self.x = torch.zeros((1, 4) + tuple(latent_hw), device=dev)
+        self.unet_in = torch.zeros((B, in_ch) + tuple(latent_hw), device=dev)
+        self.tbuf = torch.zeros(1, device=dev)
+        self.scal = torch.zeros(6, device=dev)
+        self.graph = None
+        if not graph:
+            return
+        for k, v in enumerate((1.0, 1.0, 0.0, 1.0, 0.0, 1.0)):       # a finite warm-up update
+            self.scal[k].fill_(v)
+        from .. import ops as _ops
+        from .. import streams as _streams
+        scope_before, _ops.ZERO_SCOPE = _ops.ZERO_SCOPE, ('graph', id(self))
+        feed = sd._noise_feed = _NoiseFeed()
+        cur = torch.cuda.current_stream()
+        side = _streams.get(dev, 'capture')
+        side.wait_stream(cur)
+        try:
+            with torch.cuda.stream(side):
+                self._body()                                    # warm-up: packs weights, fills the prompt's K / V cache
+            cur.wait_stream(side)
+            assert not feed.specs, 'a sampler step draws nothing'
+            feed.freeze(dev)
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph, capture_error_mode='thread_local'):
+                self._body()
+        finally:
+            sd._noise_feed = None
+            _ops.ZERO_SCOPE = scope_before
+        self._scope = ('graph', id(self))
+        from . import transformer_cm
+        self.pinned = transformer_cm.prompt_entries(sd.unet) if isinstance(sd.unet, nn.Module) else []
+
+    def __del__(self):
+        try:
+            from .. import ops as _ops
+            for k in [k for k in _ops._ZERO_WORDS if k[2] == getattr(self, '_scope', None)]:
+                del _ops._ZERO_WORDS[k]
+        except Exception:                                       # noqa: BLE001 -- interpreter shutdown
+            pass
+
+    def _body(self):
+        from .. import ops
+        sd = self.sd
+        eps = sd.unet(self.unet_in.to(sd.precision_t), self.tbuf, encoder_hidden_states=self.emb,
+                      cross_attention_kwargs=None, return_dict=False)[0]
+        ops.ddim_cfg_step(eps, self.x, self.scal, self.unet_in, self.tbuf)
+
+    def run(self, latents, cond, timesteps, step_ratio, guidance_scale):
+        """Denoises `latents` [1, 4, h, w] over `timesteps`; cond [B, in_ch - 4, h, w] (mask | masked-image latents) or None.
+        Returns the final latents (a new tensor) and the number of steps run."""
+        self.x.copy_(latents)
+        self.unet_in[:, :4].copy_(latents.expand(self.unet_in.shape[0], -1, -1, -1))
+        if cond is not None:
+            self.unet_in[:, 4:].copy_(cond)                     # once per call, not per step
+        self.tbuf.fill_(float(timesteps[0]))
+        alphas = self.sd._alphas_host
+        for k, t in enumerate(timesteps):
+            t_next = timesteps[k + 1] if k + 1 < len(timesteps) else 0
+            # kernel-argument fills, as _GraphedStep.run fills its scal (no host -> device copy)
+            for j, v in enumerate(ddim_step_scalars(alphas, t, step_ratio, guidance_scale, t_next)):
+                self.scal[j].fill_(v)
+            if self.graph is not None:
+                self.graph.replay()
+            else:
+                self._body()
+        return self.x.clone(), len(timesteps)
+
+
 def seed_everything(seed):
     torch.manual_seed(seed)
     torch.cuda.manual_seed(seed)
@@ -376,6 +488,8 @@ class StableDiffusion(nn.Module):
                 use_graphs = False
         self.use_graphs = bool(use_graphs)
         self._graphs = {}
+        self._sample_steps = {}          # the 2D sampler's steps (captured when use_graphs), keyed like _graph_for's graphs
+        self._embeds = {}                # (negative, positive) prompt -> [2, 77, 768] of prompt_to_img
         self.scaling_factor = float(getattr(getattr(self.vae, 'config', None), 'scaling_factor', 0.18215))
 
     def release_graphs(self):
@@ -386,6 +500,7 @@ class StableDiffusion(nn.Module):
         (ops._stash_budget).  The next step of a released key captures again."""
         import gc
         self._graphs.clear()
+        self._sample_steps.clear()
         gc.collect()
         if torch.device(self.device).type == 'cuda':
             torch.cuda.empty_cache()
@@ -616,3 +731,145 @@ class StableDiffusion(nn.Module):
             loss = SpecifyGradient.apply(latents, grad.clone(), prep[1])
             (weight * loss).sum().backward()
         return x.grad
+
+    # -- the 2D sampler: the reference's remaining public methods (DS_NeRF/guidance/sd_utils.py:111-117, :602-666) and an
+    # inpainting preview on the SDS step's own conditioning ------------------------------------------------------------
+    # Scheduler: DDIM, eta = 0, over this object's alphas_cumprod with the SD-1.x settings (ddim_timesteps); no checkpoint
+    # scheduler config is read (PNDM and the other schedulers are not provided).  The UNet runs at 512 x 512 only (64 x 64
+    # latents, the shape the SDS step proves); each denoising step is the UNet's CFG forward plus ONE update launch
+    # (ops.ddim_cfg_step), captured once as a hipGraph and replayed when use_graphs is set.
+    MAX_SAMPLER_GRAPHS = 4
+
+    @torch.no_grad()
+    def get_text_embeds(self, prompt):
+        """text_encoder(tokenizer(prompt)) -> [B, 77, 768] for a prompt or a list of prompts."""
+        prompts = [prompt] if isinstance(prompt, str) else list(prompt)
+        nets = self.networks
+        return torch.cat([nets.text_encoder(nets.tokenizer(p).to(self.device)) for p in prompts], 0)
+
+    @torch.no_grad()
+    def encode_imgs(self, imgs):
+        """imgs [B, 3, H, W] in [0, 1] -> scaling_factor * posterior.sample() of 2 imgs - 1 (one draw through _randn)."""
+        return self._encode_vae_image(2 * imgs - 1)
+
+    @torch.no_grad()
+    def decode_latents(self, latents):
+        """((vae.decode(latents / scaling_factor)) / 2 + 0.5).clamp(0, 1) -> [B, 3, 8h, 8w]; on the device the decoder's tail
+        and the post-processing are one launch (AutoencoderKL.decode_image)."""
+        return self._decode(latents)[0]
+
+    def _decode(self, latents, uint8=False):
+        z = latents / self.scaling_factor
+        if hasattr(self.vae, 'decode_image'):
+            return self.vae.decode_image(z, uint8)
+        out = self.vae.decode(z)
+        img = ((out.sample if hasattr(out, 'sample') else out[0]) / 2 + 0.5).clamp(0, 1)
+        return img, ((img * 255).round().to(torch.uint8).permute(0, 2, 3, 1).contiguous() if uint8 else None)
+
+    def _sampler_step(self, emb, cfg, latent_hw, in_ch):
+        stream = torch.cuda.current_stream(emb.device).cuda_stream if emb.is_cuda else 0
+        key = (emb.data_ptr(), emb._version, tuple(emb.shape), bool(cfg), tuple(latent_hw), int(in_ch), stream, self.use_graphs)
+        step = self._sample_steps.get(key)
+        if step is None:
+            while len(self._sample_steps) >= self.MAX_SAMPLER_GRAPHS:
+                self._sample_steps.pop(next(iter(self._sample_steps)))
+            step = _SamplerStep(self, emb, cfg, latent_hw, in_ch, graph=self.use_graphs)
+            self._sample_steps[key] = step
+        return step
+
+    def _denoise(self, latents, emb, cfg, guidance_scale, cond, timesteps, step_ratio):
+        in_ch = 4 if cond is None else 4 + cond.shape[1]
+        step = self._sampler_step(emb, cfg, latents.shape[2:], in_ch)
+        out, n = step.run(latents.float().contiguous(), None if cond is None else cond.float(), timesteps, step_ratio,
+                          guidance_scale)
+        self.last_sample_steps = n
+        return out
+
+    @staticmethod
+    def _check_size(height, width):
+        if (int(height), int(width)) != (512, 512):
+            raise NotImplementedError(f'the sampler runs at 512 x 512 (the UNet is proven at 64 x 64 latents), got {height} x {width}')
+
+    @torch.no_grad()
+    def produce_latents(self, text_embeddings, height=512, width=512, num_inference_steps=50, guidance_scale=7.5, latents=None,
+                        *, mask=None, masked_image_latents=None):
+        """DDIM from noise (or `latents` [1, 4, h, w]) -> latents [1, 4, h, w].  text_embeddings [2, 77, 768] = (negative,
+        positive): classifier-free guidance; [1, 77, 768]: none.  The reference draws `unet.in_channels` = 9-channel noise and
+        hands a 4-channel prediction to the scheduler, which fails on the shapes; here the noise has 4 channels and the
+        9-channel UNet's conditioning defaults to a full mask (generate everywhere) and the encode of a zero image -- what
+        _prepare feeds the SDS step for a full mask (masked image = image * (mask < 0.5) = 0, no [-1, 1] rescale).  Draw
+        order: the default masked-image encode, then the noise."""
+        self._check_size(height, width)
+        B = text_embeddings.shape[0]
+        if B not in (1, 2):
+            raise ValueError('produce_latents takes one prompt at a time: text_embeddings [2, 77, 768] (CFG) or [1, 77, 768]')
+        cfg = B == 2
+        h, w = height // 8, width // 8
+        in_ch = int(getattr(self.unet, 'in_channels', 4))
+        emb = text_embeddings.to(self.device)
+        cond = None
+        if in_ch != 4:
+            if masked_image_latents is None:
+                zero = torch.zeros(1, 3, height, width, device=self.device)
+                masked_image_latents = self._encode_vae_image(zero)
+            if mask is None:
+                mask = torch.ones(1, 1, h, w, device=self.device)
+            cond = torch.cat([mask.float().expand(B, -1, -1, -1), masked_image_latents.float().expand(B, -1, -1, -1)], 1)
+        if latents is None:
+            latents = self._randn((1, 4, h, w))
+        timesteps, ratio = ddim_timesteps(num_inference_steps, self.num_train_timesteps)
+        return self._denoise(latents, emb, cfg, guidance_scale, cond, timesteps, ratio)
+
+    def _prompt_pair(self, negative, positive):
+        """[2, 77, 768] = (negative, positive), one stable tensor per pair (the captured sampler step is keyed by it)."""
+        key = (negative, positive)
+        if key not in self._embeds:
+            self._embeds[key] = torch.cat([self.get_text_embeds([negative]), self.get_text_embeds([positive])], 0)
+        return self._embeds[key]
+
+    @torch.no_grad()
+    def prompt_to_img(self, prompts, negative_prompts='', height=512, width=512, num_inference_steps=50, guidance_scale=7.5,
+                      latents=None):
+        """prompts -> uint8 [B, H, W, 3] (numpy, as the reference returns), one prompt at a time (CFG batch 2)."""
+        prompts = [prompts] if isinstance(prompts, str) else list(prompts)
+        negs = [negative_prompts] if isinstance(negative_prompts, str) else list(negative_prompts)
+        if len(negs) == 1:
+            negs = negs * len(prompts)
+        out = []
+        for p, q in zip(prompts, negs):
+            lat = self.produce_latents(self._prompt_pair(q, p), height=height, width=width, num_inference_steps=num_inference_steps,
+                                       guidance_scale=guidance_scale, latents=latents)
+            out.append(self._decode(lat, uint8=True)[1])
+        return torch.cat(out, 0).cpu().numpy()
+
+    @torch.no_grad()
+    def inpaint(self, image, mask, prompt, negative_prompt='', num_inference_steps=50, guidance_scale=7.5, strength=1.0,
+                latents=None):
+        """What the prior paints into `mask` (1 = generate) for `prompt`: image [1, 3, H, W] in [0, 1], mask [1, 1, H, W] ->
+        [1, 3, 512, 512] in [0, 1].  The conditioning (resize to 512, masked image WITHOUT the [-1, 1] rescale, 64 x 64
+        nearest mask, masked-image encode) is built by _prepare, the code that feeds the SDS terms, so the preview shows what
+        the prior is conditioned on in training.  strength < 1 starts from add_noise(encode(image), noise, timesteps[0]) over
+        the last int(n * strength) timesteps; unlike the reference's pipeline call (pipeline_sd_inpainting.py:978) strength is
+        NOT doubled.  negative_prompt '' is the SDS step's own unconditional prompt.
+        Draw order: _prepare's draws, the image encode (strength < 1 only), the initial noise; the steps draw nothing."""
+        _check_strength(strength)
+        timesteps, ratio = ddim_timesteps(num_inference_steps, self.num_train_timesteps)
+        timesteps, _ = get_timesteps(timesteps, len(timesteps), strength)
+        if not timesteps:
+            raise ValueError(f'strength {strength} leaves no step of {num_inference_steps}')
+        init_image, mask64, masked_latents, emb, cfg = self._prepare(image, mask, prompt, guidance_scale)
+        join, self._join = self._join, None
+        if join is not None:
+            torch.cuda.current_stream(masked_latents.device).wait_stream(join)
+        if cfg and negative_prompt != '':
+            emb = self._prompt_pair(negative_prompt, prompt)
+        image_latents = self._encode_vae_image(init_image) if strength < 1.0 else None
+        noise = self._randn((1, 4, 64, 64)) if latents is None else latents.to(self.device).float()
+        if image_latents is not None:
+            a = self._alphas_host[timesteps[0]]
+            x = _AddNoise.apply(image_latents.float(), noise, a ** 0.5, (1.0 - a) ** 0.5)
+        else:
+            x = noise
+        cond = torch.cat([mask64.float(), masked_latents.float()], 1)
+        lat = self._denoise(x, emb, cfg, guidance_scale, cond, timesteps, ratio)
+        return self.decode_latents(lat)

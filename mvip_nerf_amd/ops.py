@@ -1692,3 +1692,42 @@ def softmax_rows_backward(P, dP, scale):
     dS = torch.empty_like(Pc)
     call('mvip_softmax_rows_backward', ptr(Pc), ptr(dc), Pc.shape[0], Pc.shape[1], float(scale), ptr(dS), stream())
     return dS
+
+
+# The 2D inpainting sampler (guidance/sd_utils.StableDiffusion.decode_latents / produce_latents / inpaint) ------------------
+
+def vae_decoder_head(x, norm, conv, uint8=False):
+    """clamp(conv(silu(norm(x))) / 2 + 0.5, 0, 1) for the VAE decoder's conv_norm_out / conv_out (3 output channels) and
+    decode_latents' post-processing: GroupNorm statistics by one pass over x, then ONE launch (csrc/sd_sample.hip) that reads
+    x once more -- no im2col planes.  Returns (img [N, 3, H, W] fp32, img_u8 [N, H, W, 3] = rint(255 img) or None).
+    Forward only; `prec` is the current precision() (1 = the --fp16 mode's fp16 products)."""
+    xc = _f32c(x.detach())
+    N, C, H, W = xc.shape
+    G, dev = norm.num_groups, xc.device
+    if conv.out_channels != 3 or conv.in_channels != C or conv.kernel_size != (3, 3) or conv.padding != (1, 1):
+        raise _lib.MvipError('vae_decoder_head: expects a 3x3 / padding 1 convolution to 3 channels')
+    mean, rstd = _gn_stats(xc, N, C, H, W, G, norm.eps, _gn_workspace(N, C, H * W, dev))
+    img = torch.empty((N, 3, H, W), device=dev, dtype=_F32)
+    u8 = torch.empty((N, H, W, 3), device=dev, dtype=torch.uint8) if uint8 else None
+    call('mvip_vae_decoder_head', ptr(xc), ptr(mean), ptr(rstd), ptr(_f32c(norm.weight.detach())), ptr(_f32c(norm.bias.detach())),
+         ptr(_f32c(conv.weight.detach())), ptr(_f32c(conv.bias.detach())), N, C, H, W, G, 0, ptr(img),
+         ptr(u8, torch.uint8), _prec(), stream())
+    return img, u8
+
+
+def ddim_cfg_step(eps, x, scal, unet_in=None, t_out=None):
+    """One DDIM update (eta = 0) with classifier-free guidance in place on x [1, 4, h, w]: eps [2, 4, h, w] (uncond, cond) or
+    [1, 4, h, w]; scal (device, 6 floats) = {g, sqrt(abar_t), sqrt(1 - abar_t), sqrt(abar_prev), sqrt(1 - abar_prev), t_next}.
+    Also writes the new latents into channels 0..3 of the UNet input unet_in [1 + cfg, C_in, h, w] and t_next into t_out."""
+    if not (x.is_contiguous() and x.dtype == _F32 and x.dim() == 4 and x.shape[:2] == (1, 4)):
+        raise _lib.MvipError('ddim_cfg_step: x must be a dense fp32 [1, 4, h, w] tensor (updated in place)')
+    e = _f32c(eps)
+    hw = x.shape[2] * x.shape[3]
+    cfg = e.shape[0] == 2
+    if tuple(e.shape[1:]) != tuple(x.shape[1:]) or e.shape[0] not in (1, 2):
+        raise _lib.MvipError(f'ddim_cfg_step: eps {tuple(e.shape)} does not match x {tuple(x.shape)}')
+    if unet_in is not None and (unet_in.shape[0] != e.shape[0] or tuple(unet_in.shape[2:]) != tuple(x.shape[2:])):
+        raise _lib.MvipError(f'ddim_cfg_step: UNet input {tuple(unet_in.shape)} does not match eps {tuple(e.shape)}')
+    call('mvip_ddim_cfg_step', ptr(e), int(cfg), ptr(scal), ptr(x), hw, ptr(unet_in),
+         0 if unet_in is None else unet_in.shape[1], ptr(t_out), stream())
+    return x
