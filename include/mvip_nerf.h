@@ -655,6 +655,31 @@ int mvip_skinny_wgrad(const float *dY, const float *X, int64_t M, int64_t N, int
 int mvip_skinny_linear(const float *w, int64_t w_sm, int64_t w_sn, const float *X, int64_t M, int64_t N, int64_t P,
                        int relu, float *Y, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Marching-cubes mesh extraction (beyond the reference: it has no mesh export; csrc/mcubes.hip,
+ * mvip_nerf_amd/mesh.py).  grid [nx,ny,nz] fp32, C-contiguous (z fastest), 2 <= n <= 768 per axis;
+ * point (i,j,k) sits at bmin + (i,j,k) * (bmax - bmin) / (n - 1).  A corner is inside iff v >= iso
+ * (iso > 0); an edge crosses iff exactly one end is inside; t = (iso - v0) / (v1 - v0),
+ * p = p0 + t (p1 - p0).  Vertices are ordered by (point linear index, axis x < y < z), triangles by
+ * (cell linear index, table slot), faces counter-clockwise seen from outside (decreasing sigma).
+ * tri_table: 256 x 16 int8 (-1 terminated; corner c = dx + 2 dy + 4 dz, edge e = 4 axis + r), 16-byte
+ * aligned DEVICE memory, the table of mvip_nerf_amd/mesh.py.
+ *
+ * mvip_mcubes_groups: G, the workgroup count of a grid (-1 for a shape outside the limits).
+ * mvip_mcubes_count: flags [nx*ny*nz] uint16 (cube index | edge flags << 8), wg [G,2] int64 (vertex and
+ *   triangle offsets of each workgroup), totals [3] int64 = (vertices, triangles, non-finite flag).  The
+ *   caller reads totals back once to allocate the outputs.  No empty form (every axis has >= 2 points).
+ * mvip_mcubes_emit: from count's flags / wg and its totals (n_verts, n_tris): vid [nx*ny*nz] int32 (first
+ *   vertex id of each point), verts / normals [n_verts,3] (normals: -grad sigma, central differences at
+ *   the edge ends, interpolated, normalised), faces [n_tris,3] int32.  n_verts = n_tris = 0 is the empty
+ *   call (MVIP_OK, nothing written); n_tris must be <= 2^31 - 1. */
+int64_t mvip_mcubes_groups(int nx, int ny, int nz);
+int mvip_mcubes_count(const float *grid, int nx, int ny, int nz, float iso, const void *tri_table, void *flags,
+                      int64_t *wg, int64_t *totals, void *stream);
+int mvip_mcubes_emit(const float *grid, int nx, int ny, int nz, float iso, float x0, float y0, float z0, float x1,
+                     float y1, float z1, const void *tri_table, const void *flags, const int64_t *wg, int64_t n_verts,
+                     int64_t n_tris, int *vid, float *verts, float *normals, int *faces, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -153,6 +153,10 @@ _SIGNATURES = {
                                                    _c_f]),
     'mvip_groupnorm_split_planes_moments_out': (_int, [_c_f, _c_f, _c_f, _c_f, _flt, _i64, _i64, _i64, _int, _int, _c_f, _c_f, _c_f,
                                                        _int, _c_f]),
+    'mvip_mcubes_groups': (_i64, [_int, _int, _int]),
+    'mvip_mcubes_count': (_int, [_c_f, _int, _int, _int, _flt, _c_f, _c_f, _c_f, _c_f, _c_f]),
+    'mvip_mcubes_emit': (_int, [_c_f, _int, _int, _int, _flt, _flt, _flt, _flt, _flt, _flt, _flt, _c_f, _c_f, _c_f, _i64, _i64,
+                                _c_f, _c_f, _c_f, _c_f, _c_f]),
 }
 
 # every symbol include/mvip_nerf.h declares; tests check the built library exports all of them

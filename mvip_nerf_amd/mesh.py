@@ -1,0 +1,467 @@
+"""Triangle-mesh export of a trained radiance field (beyond the reference: MVIP-NeRF only renders depth / normal images).
+
+density_grid() samples sigma on a dense grid with the model's own no-grad query path (`render_kwargs['network_query_fn']`:
+the fused 8x256 MLP kernel for create_nerf, the fused hash-grid kernel for create_nerf_tcnn); marching_cubes() turns it into
+an indexed, crack-free triangle mesh with the HIP passes of csrc/mcubes.hip; extract_mesh() does both and colours the
+vertices; save_ply() writes the result.  There is no CPU path: grids and meshes live on the device until save_ply.
+
+Conventions (shared with csrc/mcubes.hip and the test restatement tests/mc_numpy.py): grid [nx, ny, nz], z fastest; point
+(i, j, k) sits at bmin + (i, j, k) * (bmax - bmin) / (n - 1), in fp32 arithmetic; a corner is inside iff sigma >= threshold
+(threshold > 0); t = (threshold - v0) / (v1 - v0), p = p0 + t (p1 - p0); vertices are ordered by (point, axis), triangles
+by (cell, table slot); faces are counter-clockwise seen from outside (decreasing sigma), so a closed surface has positive
+signed volume.  Normals are -grad sigma (central differences), normalised.
+"""
+import collections
+import math
+
+import numpy as np
+import torch
+
+from . import ops
+
+# Corner c of a cell = (dx, dy, dz) with c = dx + 2 dy + 4 dz; bit c of the cube index is set iff corner c is inside.
+# Edge e = 4 * axis + r runs from the corner with the two other offsets (r & 1, r >> 1), in axis order, along `axis`.
+# Row `cube` lists up to five triangles as edge triples, -1 terminated.  The table was derived, not transcribed: on every
+# cell face the crossing edges are paired so that each inside corner of an ambiguous face (two inside corners on a
+# diagonal) is cut off on its own; that choice depends on the face's four corners alone, so the two cells sharing a face
+# cut it the same way and the surface has no cracks.  The face segments chain into closed loops; each loop is triangulated
+# (a fan where one qualifies) with no diagonal between two edges of one cell face, since the neighbour across that face
+# could draw the same diagonal and the mesh edge would then have four triangles.  Every triangle is wound
+# counter-clockwise seen from the outside corners.
+# tests/test_mesh_cpu.py checks closedness, orientation and every ambiguous configuration on this table.
+TRI_TABLE = (
+    (-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (0, 4, 8, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (0, 9, 5, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (4, 8, 9, 4, 9, 5, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (1, 10, 4, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (0, 1, 10, 0, 10, 8, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (0, 9, 5, 1, 10, 4, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (1, 10, 8, 1, 8, 9, 1, 9, 5, -1, -1, -1, -1, -1, -1, -1),
+    (1, 5, 11, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (0, 4, 8, 1, 5, 11, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (0, 9, 11, 0, 11, 1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (1, 4, 8, 1, 8, 9, 1, 9, 11, -1, -1, -1, -1, -1, -1, -1),
+    (4, 5, 11, 4, 11, 10, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (0, 5, 11, 0, 11, 10, 0, 10, 8, -1, -1, -1, -1, -1, -1, -1),
+    (0, 9, 11, 0, 11, 10, 0, 10, 4, -1, -1, -1, -1, -1, -1, -1),
+    (8, 9, 11, 8, 11, 10, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (2, 8, 6, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (0, 4, 6, 0, 6, 2, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (0, 9, 5, 2, 8, 6, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (2, 9, 5, 2, 5, 4, 2, 4, 6, -1, -1, -1, -1, -1, -1, -1),
+    (1, 10, 4, 2, 8, 6, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (0, 1, 10, 0, 10, 6, 0, 6, 2, -1, -1, -1, -1, -1, -1, -1),
+    (0, 9, 5, 1, 10, 4, 2, 8, 6, -1, -1, -1, -1, -1, -1, -1),
+    (1, 10, 6, 1, 6, 2, 1, 2, 9, 1, 9, 5, -1, -1, -1, -1),
+    (1, 5, 11, 2, 8, 6, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (0, 4, 6, 0, 6, 2, 1, 5, 11, -1, -1, -1, -1, -1, -1, -1),
+    (0, 9, 11, 0, 11, 1, 2, 8, 6, -1, -1, -1, -1, -1, -1, -1),
+    (1, 4, 6, 1, 6, 2, 1, 2, 9, 1, 9, 11, -1, -1, -1, -1),
+    (2, 8, 6, 4, 5, 11, 4, 11, 10, -1, -1, -1, -1, -1, -1, -1),
+    (0, 5, 11, 0, 11, 10, 0, 10, 6, 0, 6, 2, -1, -1, -1, -1),
+    (0, 9, 11, 0, 11, 10, 0, 10, 4, 2, 8, 6, -1, -1, -1, -1),
+    (2, 9, 11, 2, 11, 10, 2, 10, 6, -1, -1, -1, -1, -1, -1, -1),
+    (2, 7, 9, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (0, 4, 8, 2, 7, 9, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (0, 2, 7, 0, 7, 5, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (2, 7, 5, 2, 5, 4, 2, 4, 8, -1, -1, -1, -1, -1, -1, -1),
+    (1, 10, 4, 2, 7, 9, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (0, 1, 10, 0, 10, 8, 2, 7, 9, -1, -1, -1, -1, -1, -1, -1),
+    (0, 2, 7, 0, 7, 5, 1, 10, 4, -1, -1, -1, -1, -1, -1, -1),
+    (1, 10, 8, 1, 8, 2, 1, 2, 7, 1, 7, 5, -1, -1, -1, -1),
+    (1, 5, 11, 2, 7, 9, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (0, 4, 8, 1, 5, 11, 2, 7, 9, -1, -1, -1, -1, -1, -1, -1),
+    (0, 2, 7, 0, 7, 11, 0, 11, 1, -1, -1, -1, -1, -1, -1, -1),
+    (1, 4, 8, 1, 8, 2, 1, 2, 7, 1, 7, 11, -1, -1, -1, -1),
+    (2, 7, 9, 4, 5, 11, 4, 11, 10, -1, -1, -1, -1, -1, -1, -1),
+    (0, 5, 11, 0, 11, 10, 0, 10, 8, 2, 7, 9, -1, -1, -1, -1),
+    (0, 2, 7, 0, 7, 11, 0, 11, 10, 0, 10, 4, -1, -1, -1, -1),
+    (2, 7, 11, 2, 11, 10, 2, 10, 8, -1, -1, -1, -1, -1, -1, -1),
+    (6, 7, 9, 6, 9, 8, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (0, 4, 6, 0, 6, 7, 0, 7, 9, -1, -1, -1, -1, -1, -1, -1),
+    (0, 8, 6, 0, 6, 7, 0, 7, 5, -1, -1, -1, -1, -1, -1, -1),
+    (4, 6, 7, 4, 7, 5, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (1, 10, 4, 6, 7, 9, 6, 9, 8, -1, -1, -1, -1, -1, -1, -1),
+    (0, 1, 10, 0, 10, 6, 0, 6, 7, 0, 7, 9, -1, -1, -1, -1),
+    (0, 8, 6, 0, 6, 7, 0, 7, 5, 1, 10, 4, -1, -1, -1, -1),
+    (1, 10, 6, 1, 6, 7, 1, 7, 5, -1, -1, -1, -1, -1, -1, -1),
+    (1, 5, 11, 6, 7, 9, 6, 9, 8, -1, -1, -1, -1, -1, -1, -1),
+    (0, 4, 6, 0, 6, 7, 0, 7, 9, 1, 5, 11, -1, -1, -1, -1),
+    (0, 8, 6, 0, 6, 7, 0, 7, 11, 0, 11, 1, -1, -1, -1, -1),
+    (1, 4, 6, 1, 6, 7, 1, 7, 11, -1, -1, -1, -1, -1, -1, -1),
+    (4, 5, 11, 4, 11, 10, 6, 7, 9, 6, 9, 8, -1, -1, -1, -1),
+    (0, 5, 11, 0, 11, 10, 0, 10, 6, 0, 6, 7, 0, 7, 9, -1),
+    (0, 8, 6, 0, 6, 7, 0, 7, 11, 0, 11, 10, 0, 10, 4, -1),
+    (6, 7, 11, 6, 11, 10, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (3, 6, 10, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (0, 4, 8, 3, 6, 10, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (0, 9, 5, 3, 6, 10, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (3, 6, 10, 4, 8, 9, 4, 9, 5, -1, -1, -1, -1, -1, -1, -1),
+    (1, 3, 6, 1, 6, 4, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (0, 1, 3, 0, 3, 6, 0, 6, 8, -1, -1, -1, -1, -1, -1, -1),
+    (0, 9, 5, 1, 3, 6, 1, 6, 4, -1, -1, -1, -1, -1, -1, -1),
+    (1, 3, 6, 1, 6, 8, 1, 8, 9, 1, 9, 5, -1, -1, -1, -1),
+    (1, 5, 11, 3, 6, 10, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (0, 4, 8, 1, 5, 11, 3, 6, 10, -1, -1, -1, -1, -1, -1, -1),
+    (0, 9, 11, 0, 11, 1, 3, 6, 10, -1, -1, -1, -1, -1, -1, -1),
+    (1, 4, 8, 1, 8, 9, 1, 9, 11, 3, 6, 10, -1, -1, -1, -1),
+    (3, 6, 4, 3, 4, 5, 3, 5, 11, -1, -1, -1, -1, -1, -1, -1),
+    (0, 5, 11, 0, 11, 3, 0, 3, 6, 0, 6, 8, -1, -1, -1, -1),
+    (0, 9, 11, 0, 11, 3, 0, 3, 6, 0, 6, 4, -1, -1, -1, -1),
+    (3, 6, 8, 3, 8, 9, 3, 9, 11, -1, -1, -1, -1, -1, -1, -1),
+    (2, 8, 10, 2, 10, 3, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (0, 4, 10, 0, 10, 3, 0, 3, 2, -1, -1, -1, -1, -1, -1, -1),
+    (0, 9, 5, 2, 8, 10, 2, 10, 3, -1, -1, -1, -1, -1, -1, -1),
+    (2, 9, 5, 2, 5, 4, 2, 4, 10, 2, 10, 3, -1, -1, -1, -1),
+    (1, 3, 2, 1, 2, 8, 1, 8, 4, -1, -1, -1, -1, -1, -1, -1),
+    (0, 1, 3, 0, 3, 2, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (0, 9, 5, 1, 3, 2, 1, 2, 8, 1, 8, 4, -1, -1, -1, -1),
+    (1, 3, 2, 1, 2, 9, 1, 9, 5, -1, -1, -1, -1, -1, -1, -1),
+    (1, 5, 11, 2, 8, 10, 2, 10, 3, -1, -1, -1, -1, -1, -1, -1),
+    (0, 4, 10, 0, 10, 3, 0, 3, 2, 1, 5, 11, -1, -1, -1, -1),
+    (0, 9, 11, 0, 11, 1, 2, 8, 10, 2, 10, 3, -1, -1, -1, -1),
+    (4, 10, 3, 4, 3, 2, 4, 2, 9, 4, 9, 11, 4, 11, 1, -1),
+    (2, 8, 4, 2, 4, 5, 2, 5, 11, 2, 11, 3, -1, -1, -1, -1),
+    (0, 5, 11, 0, 11, 3, 0, 3, 2, -1, -1, -1, -1, -1, -1, -1),
+    (11, 3, 2, 11, 2, 8, 11, 8, 4, 11, 4, 0, 11, 0, 9, -1),
+    (2, 9, 11, 2, 11, 3, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (2, 7, 9, 3, 6, 10, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (0, 4, 8, 2, 7, 9, 3, 6, 10, -1, -1, -1, -1, -1, -1, -1),
+    (0, 2, 7, 0, 7, 5, 3, 6, 10, -1, -1, -1, -1, -1, -1, -1),
+    (2, 7, 5, 2, 5, 4, 2, 4, 8, 3, 6, 10, -1, -1, -1, -1),
+    (1, 3, 6, 1, 6, 4, 2, 7, 9, -1, -1, -1, -1, -1, -1, -1),
+    (0, 1, 3, 0, 3, 6, 0, 6, 8, 2, 7, 9, -1, -1, -1, -1),
+    (0, 2, 7, 0, 7, 5, 1, 3, 6, 1, 6, 4, -1, -1, -1, -1),
+    (1, 3, 6, 1, 6, 8, 1, 8, 2, 1, 2, 7, 1, 7, 5, -1),
+    (1, 5, 11, 2, 7, 9, 3, 6, 10, -1, -1, -1, -1, -1, -1, -1),
+    (0, 4, 8, 1, 5, 11, 2, 7, 9, 3, 6, 10, -1, -1, -1, -1),
+    (0, 2, 7, 0, 7, 11, 0, 11, 1, 3, 6, 10, -1, -1, -1, -1),
+    (1, 4, 8, 1, 8, 2, 1, 2, 7, 1, 7, 11, 3, 6, 10, -1),
+    (2, 7, 9, 3, 6, 4, 3, 4, 5, 3, 5, 11, -1, -1, -1, -1),
+    (0, 5, 11, 0, 11, 3, 0, 3, 6, 0, 6, 8, 2, 7, 9, -1),
+    (0, 2, 7, 0, 7, 11, 0, 11, 3, 0, 3, 6, 0, 6, 4, -1),
+    (11, 3, 6, 11, 6, 8, 11, 8, 2, 11, 2, 7, -1, -1, -1, -1),
+    (3, 7, 9, 3, 9, 8, 3, 8, 10, -1, -1, -1, -1, -1, -1, -1),
+    (0, 4, 10, 0, 10, 3, 0, 3, 7, 0, 7, 9, -1, -1, -1, -1),
+    (0, 8, 10, 0, 10, 3, 0, 3, 7, 0, 7, 5, -1, -1, -1, -1),
+    (3, 7, 5, 3, 5, 4, 3, 4, 10, -1, -1, -1, -1, -1, -1, -1),
+    (1, 3, 7, 1, 7, 9, 1, 9, 8, 1, 8, 4, -1, -1, -1, -1),
+    (0, 1, 3, 0, 3, 7, 0, 7, 9, -1, -1, -1, -1, -1, -1, -1),
+    (8, 4, 1, 8, 1, 3, 8, 3, 7, 8, 7, 5, 8, 5, 0, -1),
+    (1, 3, 7, 1, 7, 5, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (1, 5, 11, 3, 7, 9, 3, 9, 8, 3, 8, 10, -1, -1, -1, -1),
+    (0, 4, 10, 0, 10, 3, 0, 3, 7, 0, 7, 9, 1, 5, 11, -1),
+    (0, 8, 10, 0, 10, 3, 0, 3, 7, 0, 7, 11, 0, 11, 1, -1),
+    (4, 10, 3, 4, 3, 7, 4, 7, 11, 4, 11, 1, -1, -1, -1, -1),
+    (3, 7, 9, 3, 9, 8, 3, 8, 4, 3, 4, 5, 3, 5, 11, -1),
+    (0, 5, 11, 0, 11, 3, 0, 3, 7, 0, 7, 9, -1, -1, -1, -1),
+    (0, 8, 4, 3, 7, 11, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (3, 7, 11, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (3, 11, 7, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (0, 4, 8, 3, 11, 7, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (0, 9, 5, 3, 11, 7, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (3, 11, 7, 4, 8, 9, 4, 9, 5, -1, -1, -1, -1, -1, -1, -1),
+    (1, 10, 4, 3, 11, 7, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (0, 1, 10, 0, 10, 8, 3, 11, 7, -1, -1, -1, -1, -1, -1, -1),
+    (0, 9, 5, 1, 10, 4, 3, 11, 7, -1, -1, -1, -1, -1, -1, -1),
+    (1, 10, 8, 1, 8, 9, 1, 9, 5, 3, 11, 7, -1, -1, -1, -1),
+    (1, 5, 7, 1, 7, 3, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (0, 4, 8, 1, 5, 7, 1, 7, 3, -1, -1, -1, -1, -1, -1, -1),
+    (0, 9, 7, 0, 7, 3, 0, 3, 1, -1, -1, -1, -1, -1, -1, -1),
+    (1, 4, 8, 1, 8, 9, 1, 9, 7, 1, 7, 3, -1, -1, -1, -1),
+    (3, 10, 4, 3, 4, 5, 3, 5, 7, -1, -1, -1, -1, -1, -1, -1),
+    (0, 5, 7, 0, 7, 3, 0, 3, 10, 0, 10, 8, -1, -1, -1, -1),
+    (0, 9, 7, 0, 7, 3, 0, 3, 10, 0, 10, 4, -1, -1, -1, -1),
+    (3, 10, 8, 3, 8, 9, 3, 9, 7, -1, -1, -1, -1, -1, -1, -1),
+    (2, 8, 6, 3, 11, 7, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (0, 4, 6, 0, 6, 2, 3, 11, 7, -1, -1, -1, -1, -1, -1, -1),
+    (0, 9, 5, 2, 8, 6, 3, 11, 7, -1, -1, -1, -1, -1, -1, -1),
+    (2, 9, 5, 2, 5, 4, 2, 4, 6, 3, 11, 7, -1, -1, -1, -1),
+    (1, 10, 4, 2, 8, 6, 3, 11, 7, -1, -1, -1, -1, -1, -1, -1),
+    (0, 1, 10, 0, 10, 6, 0, 6, 2, 3, 11, 7, -1, -1, -1, -1),
+    (0, 9, 5, 1, 10, 4, 2, 8, 6, 3, 11, 7, -1, -1, -1, -1),
+    (1, 10, 6, 1, 6, 2, 1, 2, 9, 1, 9, 5, 3, 11, 7, -1),
+    (1, 5, 7, 1, 7, 3, 2, 8, 6, -1, -1, -1, -1, -1, -1, -1),
+    (0, 4, 6, 0, 6, 2, 1, 5, 7, 1, 7, 3, -1, -1, -1, -1),
+    (0, 9, 7, 0, 7, 3, 0, 3, 1, 2, 8, 6, -1, -1, -1, -1),
+    (1, 4, 6, 1, 6, 2, 1, 2, 9, 1, 9, 7, 1, 7, 3, -1),
+    (2, 8, 6, 3, 10, 4, 3, 4, 5, 3, 5, 7, -1, -1, -1, -1),
+    (0, 5, 7, 0, 7, 3, 0, 3, 10, 0, 10, 6, 0, 6, 2, -1),
+    (0, 9, 7, 0, 7, 3, 0, 3, 10, 0, 10, 4, 2, 8, 6, -1),
+    (9, 7, 3, 9, 3, 10, 9, 10, 6, 9, 6, 2, -1, -1, -1, -1),
+    (2, 3, 11, 2, 11, 9, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (0, 4, 8, 2, 3, 11, 2, 11, 9, -1, -1, -1, -1, -1, -1, -1),
+    (0, 2, 3, 0, 3, 11, 0, 11, 5, -1, -1, -1, -1, -1, -1, -1),
+    (2, 3, 11, 2, 11, 5, 2, 5, 4, 2, 4, 8, -1, -1, -1, -1),
+    (1, 10, 4, 2, 3, 11, 2, 11, 9, -1, -1, -1, -1, -1, -1, -1),
+    (0, 1, 10, 0, 10, 8, 2, 3, 11, 2, 11, 9, -1, -1, -1, -1),
+    (0, 2, 3, 0, 3, 11, 0, 11, 5, 1, 10, 4, -1, -1, -1, -1),
+    (8, 2, 3, 8, 3, 11, 8, 11, 5, 8, 5, 1, 8, 1, 10, -1),
+    (1, 5, 9, 1, 9, 2, 1, 2, 3, -1, -1, -1, -1, -1, -1, -1),
+    (0, 4, 8, 1, 5, 9, 1, 9, 2, 1, 2, 3, -1, -1, -1, -1),
+    (0, 2, 3, 0, 3, 1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (1, 4, 8, 1, 8, 2, 1, 2, 3, -1, -1, -1, -1, -1, -1, -1),
+    (2, 3, 10, 2, 10, 4, 2, 4, 5, 2, 5, 9, -1, -1, -1, -1),
+    (5, 9, 2, 5, 2, 3, 5, 3, 10, 5, 10, 8, 5, 8, 0, -1),
+    (0, 2, 3, 0, 3, 10, 0, 10, 4, -1, -1, -1, -1, -1, -1, -1),
+    (2, 3, 10, 2, 10, 8, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (3, 11, 9, 3, 9, 8, 3, 8, 6, -1, -1, -1, -1, -1, -1, -1),
+    (0, 4, 6, 0, 6, 3, 0, 3, 11, 0, 11, 9, -1, -1, -1, -1),
+    (0, 8, 6, 0, 6, 3, 0, 3, 11, 0, 11, 5, -1, -1, -1, -1),
+    (3, 11, 5, 3, 5, 4, 3, 4, 6, -1, -1, -1, -1, -1, -1, -1),
+    (1, 10, 4, 3, 11, 9, 3, 9, 8, 3, 8, 6, -1, -1, -1, -1),
+    (0, 1, 10, 0, 10, 6, 0, 6, 3, 0, 3, 11, 0, 11, 9, -1),
+    (0, 8, 6, 0, 6, 3, 0, 3, 11, 0, 11, 5, 1, 10, 4, -1),
+    (6, 3, 11, 6, 11, 5, 6, 5, 1, 6, 1, 10, -1, -1, -1, -1),
+    (1, 5, 9, 1, 9, 8, 1, 8, 6, 1, 6, 3, -1, -1, -1, -1),
+    (6, 3, 1, 6, 1, 5, 6, 5, 9, 6, 9, 0, 6, 0, 4, -1),
+    (0, 8, 6, 0, 6, 3, 0, 3, 1, -1, -1, -1, -1, -1, -1, -1),
+    (1, 4, 6, 1, 6, 3, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (3, 10, 4, 3, 4, 5, 3, 5, 9, 3, 9, 8, 3, 8, 6, -1),
+    (0, 5, 9, 3, 10, 6, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (0, 8, 6, 0, 6, 3, 0, 3, 10, 0, 10, 4, -1, -1, -1, -1),
+    (3, 10, 6, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (6, 10, 11, 6, 11, 7, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (0, 4, 8, 6, 10, 11, 6, 11, 7, -1, -1, -1, -1, -1, -1, -1),
+    (0, 9, 5, 6, 10, 11, 6, 11, 7, -1, -1, -1, -1, -1, -1, -1),
+    (4, 8, 9, 4, 9, 5, 6, 10, 11, 6, 11, 7, -1, -1, -1, -1),
+    (1, 11, 7, 1, 7, 6, 1, 6, 4, -1, -1, -1, -1, -1, -1, -1),
+    (0, 1, 11, 0, 11, 7, 0, 7, 6, 0, 6, 8, -1, -1, -1, -1),
+    (0, 9, 5, 1, 11, 7, 1, 7, 6, 1, 6, 4, -1, -1, -1, -1),
+    (1, 11, 7, 1, 7, 6, 1, 6, 8, 1, 8, 9, 1, 9, 5, -1),
+    (1, 5, 7, 1, 7, 6, 1, 6, 10, -1, -1, -1, -1, -1, -1, -1),
+    (0, 4, 8, 1, 5, 7, 1, 7, 6, 1, 6, 10, -1, -1, -1, -1),
+    (0, 9, 7, 0, 7, 6, 0, 6, 10, 0, 10, 1, -1, -1, -1, -1),
+    (1, 4, 8, 1, 8, 9, 1, 9, 7, 1, 7, 6, 1, 6, 10, -1),
+    (4, 5, 7, 4, 7, 6, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (0, 5, 7, 0, 7, 6, 0, 6, 8, -1, -1, -1, -1, -1, -1, -1),
+    (0, 9, 7, 0, 7, 6, 0, 6, 4, -1, -1, -1, -1, -1, -1, -1),
+    (6, 8, 9, 6, 9, 7, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (2, 8, 10, 2, 10, 11, 2, 11, 7, -1, -1, -1, -1, -1, -1, -1),
+    (0, 4, 10, 0, 10, 11, 0, 11, 7, 0, 7, 2, -1, -1, -1, -1),
+    (0, 9, 5, 2, 8, 10, 2, 10, 11, 2, 11, 7, -1, -1, -1, -1),
+    (2, 9, 5, 2, 5, 4, 2, 4, 10, 2, 10, 11, 2, 11, 7, -1),
+    (1, 11, 7, 1, 7, 2, 1, 2, 8, 1, 8, 4, -1, -1, -1, -1),
+    (0, 1, 11, 0, 11, 7, 0, 7, 2, -1, -1, -1, -1, -1, -1, -1),
+    (0, 9, 5, 1, 11, 7, 1, 7, 2, 1, 2, 8, 1, 8, 4, -1),
+    (1, 11, 7, 1, 7, 2, 1, 2, 9, 1, 9, 5, -1, -1, -1, -1),
+    (1, 5, 7, 1, 7, 2, 1, 2, 8, 1, 8, 10, -1, -1, -1, -1),
+    (10, 1, 5, 10, 5, 7, 10, 7, 2, 10, 2, 0, 10, 0, 4, -1),
+    (7, 2, 8, 7, 8, 10, 7, 10, 1, 7, 1, 0, 7, 0, 9, -1),
+    (1, 4, 10, 2, 9, 7, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (2, 8, 4, 2, 4, 5, 2, 5, 7, -1, -1, -1, -1, -1, -1, -1),
+    (0, 5, 7, 0, 7, 2, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (7, 2, 8, 7, 8, 4, 7, 4, 0, 7, 0, 9, -1, -1, -1, -1),
+    (2, 9, 7, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (2, 6, 10, 2, 10, 11, 2, 11, 9, -1, -1, -1, -1, -1, -1, -1),
+    (0, 4, 8, 2, 6, 10, 2, 10, 11, 2, 11, 9, -1, -1, -1, -1),
+    (0, 2, 6, 0, 6, 10, 0, 10, 11, 0, 11, 5, -1, -1, -1, -1),
+    (2, 6, 10, 2, 10, 11, 2, 11, 5, 2, 5, 4, 2, 4, 8, -1),
+    (1, 11, 9, 1, 9, 2, 1, 2, 6, 1, 6, 4, -1, -1, -1, -1),
+    (1, 11, 9, 1, 9, 2, 1, 2, 6, 1, 6, 8, 1, 8, 0, -1),
+    (2, 6, 4, 2, 4, 1, 2, 1, 11, 2, 11, 5, 2, 5, 0, -1),
+    (1, 11, 5, 2, 6, 8, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (1, 5, 9, 1, 9, 2, 1, 2, 6, 1, 6, 10, -1, -1, -1, -1),
+    (0, 4, 8, 1, 5, 9, 1, 9, 2, 1, 2, 6, 1, 6, 10, -1),
+    (0, 2, 6, 0, 6, 10, 0, 10, 1, -1, -1, -1, -1, -1, -1, -1),
+    (1, 4, 8, 1, 8, 2, 1, 2, 6, 1, 6, 10, -1, -1, -1, -1),
+    (2, 6, 4, 2, 4, 5, 2, 5, 9, -1, -1, -1, -1, -1, -1, -1),
+    (5, 9, 2, 5, 2, 6, 5, 6, 8, 5, 8, 0, -1, -1, -1, -1),
+    (0, 2, 6, 0, 6, 4, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (2, 6, 8, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (8, 10, 11, 8, 11, 9, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (0, 4, 10, 0, 10, 11, 0, 11, 9, -1, -1, -1, -1, -1, -1, -1),
+    (0, 8, 10, 0, 10, 11, 0, 11, 5, -1, -1, -1, -1, -1, -1, -1),
+    (4, 10, 11, 4, 11, 5, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (1, 11, 9, 1, 9, 8, 1, 8, 4, -1, -1, -1, -1, -1, -1, -1),
+    (0, 1, 11, 0, 11, 9, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (8, 4, 1, 8, 1, 11, 8, 11, 5, 8, 5, 0, -1, -1, -1, -1),
+    (1, 11, 5, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (1, 5, 9, 1, 9, 8, 1, 8, 10, -1, -1, -1, -1, -1, -1, -1),
+    (10, 1, 5, 10, 5, 9, 10, 9, 0, 10, 0, 4, -1, -1, -1, -1),
+    (0, 8, 10, 0, 10, 1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (1, 4, 10, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (4, 5, 9, 4, 9, 8, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (0, 5, 9, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (0, 8, 4, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+    (-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1),
+)
+assert len(TRI_TABLE) == 256 and all(len(r) == 16 for r in TRI_TABLE)
+
+MAX_POINTS_PER_AXIS = 768
+
+Mesh = collections.namedtuple('Mesh', ['verts', 'faces', 'normals', 'colors'])
+
+_device_tables = {}
+
+
+def device_table(device):
+    """TRI_TABLE as a [256, 16] int8 tensor on `device`, uploaded once per device."""
+    device = torch.device(device)
+    key = (device.type, device.index)
+    if key not in _device_tables:
+        _device_tables[key] = torch.tensor(TRI_TABLE, dtype=torch.int8, device=device).contiguous()
+    return _device_tables[key]
+
+
+def _bounds(bound_min, bound_max):
+    lo = np.asarray([float(v) for v in bound_min], dtype=np.float32)
+    hi = np.asarray([float(v) for v in bound_max], dtype=np.float32)
+    if lo.shape != (3,) or hi.shape != (3,):
+        raise ValueError('bound_min / bound_max: three coordinates each')
+    if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi))):
+        raise ValueError('bound_min / bound_max must be finite')
+    if not np.all(lo < hi):
+        raise ValueError(f'bound_min {lo.tolist()} must be below bound_max {hi.tolist()} on every axis')
+    return lo, hi
+
+
+def _check_axes(shape):
+    if len(shape) != 3 or not all(2 <= int(n) <= MAX_POINTS_PER_AXIS for n in shape):
+        raise ValueError(f'grid {tuple(shape)}: three axes of 2..{MAX_POINTS_PER_AXIS} points each')
+
+
+def marching_cubes(grid, threshold, bound_min, bound_max):
+    """grid [nx, ny, nz] fp32 device tensor -> (verts [V, 3] f32, faces [F, 3] int32, normals [V, 3] f32), all on the
+    grid's device.  An empty surface gives (0, 3) tensors.  Raises ValueError for a non-finite grid, threshold <= 0,
+    bound_min >= bound_max on an axis or an axis outside 2..768 points."""
+    if not torch.is_tensor(grid):
+        raise ValueError('grid must be a torch tensor on the GPU')
+    _check_axes(grid.shape)
+    threshold = float(threshold)
+    if not (threshold > 0 and math.isfinite(threshold)):
+        raise ValueError(f'threshold must be finite and > 0, got {threshold}')
+    lo, hi = _bounds(bound_min, bound_max)
+    return ops.marching_cubes(grid, threshold, lo, hi, device_table(grid.device))
+
+
+def grid_axes(bound_min, bound_max, resolution, device):
+    """The three coordinate vectors of the grid, as the kernels compute them: x0 + i * ((x1 - x0) / (n - 1)) in fp32."""
+    lo, hi = _bounds(bound_min, bound_max)
+    res = (int(resolution),) * 3 if np.isscalar(resolution) else tuple(int(n) for n in resolution)
+    _check_axes(res)
+    axes = []
+    for a in range(3):
+        h = (hi[a] - lo[a]) / np.float32(res[a] - 1)                       # fp32, as csrc/mcubes.hip
+        axes.append(torch.arange(res[a], device=device, dtype=torch.float32) * float(h) + float(lo[a]))
+    return axes
+
+
+def _network(render_kwargs, network):
+    if render_kwargs.get('ndc', False):
+        raise ValueError('the model was trained in NDC space: its network input is not a world-space box (out of scope)')
+    if network == 'fine':
+        net = render_kwargs.get('network_fine')
+        net = render_kwargs['network_fn'] if net is None else net
+    elif network == 'coarse':
+        net = render_kwargs['network_fn']
+    else:
+        raise ValueError(f"network must be 'fine' or 'coarse', got {network!r}")
+    return net
+
+
+def _query(render_kwargs, net, pts, dirs):
+    """raw [P, C] of the model at pts [P, 3] seen along dirs [P, 3], through the model's own query function."""
+    fn = render_kwargs['network_query_fn']
+    raw = fn(pts[:, None, :], dirs if render_kwargs.get('use_viewdirs', True) else None, net)
+    return raw.reshape(pts.shape[0], -1)
+
+
+def density_grid(render_kwargs, bound_min, bound_max, resolution, network='fine', chunk=1 << 18):
+    """sigma [nx, ny, nz] fp32 on the model's device: the network's raw density output (before the renderer's relu, which
+    leaves the set sigma >= threshold > 0 unchanged) at the grid points, queried in chunks of `chunk` points with the
+    constant view direction (0, 0, 1) (sigma does not depend on it), under torch.no_grad().  `network`: 'fine' (the fine
+    network if the model has one) or 'coarse'.  resolution: an int or three point counts."""
+    net = _network(render_kwargs, network)
+    dev = next(net.parameters()).device
+    xs, ys, zs = grid_axes(bound_min, bound_max, resolution, dev)
+    nx, ny, nz = len(xs), len(ys), len(zs)
+    n = nx * ny * nz
+    chunk = int(chunk)
+    if chunk < 1:
+        raise ValueError('chunk must be >= 1')
+    sigma = torch.empty(n, device=dev, dtype=torch.float32)
+    with torch.no_grad():
+        for s in range(0, n, chunk):
+            idx = torch.arange(s, min(n, s + chunk), device=dev, dtype=torch.int64)
+            i, r = idx // (ny * nz), idx % (ny * nz)
+            pts = torch.stack([xs[i], ys[r // nz], zs[r % nz]], -1)
+            dirs = torch.zeros_like(pts)
+            dirs[:, 2] = 1.0
+            sigma[s:s + idx.shape[0]] = _query(render_kwargs, net, pts, dirs)[:, 3]
+    return sigma.view(nx, ny, nz)
+
+
+def vertex_colors(render_kwargs, verts, normals, network='fine', chunk=1 << 18):
+    """uint8 [V, 3] = sigmoid(raw[..., :3]) of the network at each vertex seen head-on (view direction = -normal)."""
+    net = _network(render_kwargs, network)
+    chunk = int(chunk)
+    rgb = torch.empty((verts.shape[0], 3), device=verts.device, dtype=torch.uint8)
+    with torch.no_grad():
+        for s in range(0, verts.shape[0], chunk):
+            raw = _query(render_kwargs, net, verts[s:s + chunk], -normals[s:s + chunk])
+            rgb[s:s + chunk] = (torch.sigmoid(raw[:, :3]) * 255.0 + 0.5).clamp(0, 255).to(torch.uint8)
+    return rgb
+
+
+def extract_mesh(render_kwargs, bound_min, bound_max, resolution=256, threshold=10.0, colors=True, network='fine',
+                 chunk=1 << 18):
+    """Mesh(verts, faces, normals, colors) of the surface sigma = threshold inside the box: marching_cubes(density_grid(...)),
+    colours from vertex_colors() (uint8 [V, 3]), or None with colors=False."""
+    grid = density_grid(render_kwargs, bound_min, bound_max, resolution, network, chunk)
+    verts, faces, normals = marching_cubes(grid, threshold, bound_min, bound_max)
+    rgb = vertex_colors(render_kwargs, verts, normals, network, chunk) if colors else None
+    return Mesh(verts, faces, normals, rgb)
+
+
+def frustum_bounds(poses, hwf, near, far):
+    """(bound_min, bound_max) float32 [3] each: the axis-aligned box of every camera's view frustum between near and far.
+    poses [N, 3, >=4] camera-to-world (run.py's convention: x right, y up, looking down -z); hwf = (H, W, focal); the
+    frustum is spanned by the rays of the corner pixels (get_rays: direction ((i - W/2) / f, -(j - H/2) / f, -1), i in
+    {0, W - 1}, j in {0, H - 1}) at depth near and far.  A default box; users usually crop tighter."""
+    P = np.asarray(poses.detach().cpu() if torch.is_tensor(poses) else poses, dtype=np.float64)
+    if P.ndim == 2:
+        P = P[None]
+    H, W, f = float(hwf[0]), float(hwf[1]), float(hwf[2])
+    if not (near < far):
+        raise ValueError('near must be < far')
+    i = np.array([0.0, W - 1.0, 0.0, W - 1.0])
+    j = np.array([0.0, 0.0, H - 1.0, H - 1.0])
+    d_cam = np.stack([(i - W * 0.5) / f, -(j - H * 0.5) / f, -np.ones(4)], -1)            # [4, 3]
+    d = np.einsum('kc,nrc->nkr', d_cam, P[:, :3, :3])                                     # [N, 4, 3]
+    o = P[:, None, :3, 3]
+    corners = np.concatenate([o + d * float(near), o + d * float(far)], 1).reshape(-1, 3)
+    return corners.min(0).astype(np.float32), corners.max(0).astype(np.float32)
+
+
+def save_ply(path, mesh):
+    """Binary little-endian PLY: float x y z, float nx ny nz, uchar red green blue (when mesh.colors is not None), and
+    `uchar int` face lists."""
+    v = np.ascontiguousarray(mesh.verts.detach().cpu().numpy() if torch.is_tensor(mesh.verts) else mesh.verts, '<f4')
+    nrm = np.ascontiguousarray(mesh.normals.detach().cpu().numpy() if torch.is_tensor(mesh.normals) else mesh.normals,
+                               '<f4')
+    f = np.ascontiguousarray(mesh.faces.detach().cpu().numpy() if torch.is_tensor(mesh.faces) else mesh.faces, '<i4')
+    c = mesh.colors
+    if c is not None:
+        c = np.ascontiguousarray(c.detach().cpu().numpy() if torch.is_tensor(c) else c, np.uint8)
+    vfields = [('x', '<f4'), ('y', '<f4'), ('z', '<f4'), ('nx', '<f4'), ('ny', '<f4'), ('nz', '<f4')]
+    if c is not None:
+        vfields += [('red', 'u1'), ('green', 'u1'), ('blue', 'u1')]
+    vert = np.empty(v.shape[0], dtype=vfields)
+    vert['x'], vert['y'], vert['z'] = v[:, 0], v[:, 1], v[:, 2]
+    vert['nx'], vert['ny'], vert['nz'] = nrm[:, 0], nrm[:, 1], nrm[:, 2]
+    if c is not None:
+        vert['red'], vert['green'], vert['blue'] = c[:, 0], c[:, 1], c[:, 2]
+    face = np.empty(f.shape[0], dtype=[('n', 'u1'), ('v', '<i4', (3,))])
+    face['n'] = 3
+    face['v'] = f
+    head = ['ply', 'format binary_little_endian 1.0', 'comment mvip_nerf_amd.mesh', f'element vertex {v.shape[0]}']
+    head += [f'property float {k}' for k in ('x', 'y', 'z', 'nx', 'ny', 'nz')]
+    if c is not None:
+        head += ['property uchar red', 'property uchar green', 'property uchar blue']
+    head += [f'element face {f.shape[0]}', 'property list uchar int vertex_indices', 'end_header']
+    with open(path, 'wb') as fh:
+        fh.write(('\n'.join(head) + '\n').encode('ascii'))
+        fh.write(vert.tobytes())
+        fh.write(face.tobytes())

@@ -1731,3 +1731,37 @@ def ddim_cfg_step(eps, x, scal, unet_in=None, t_out=None):
     call('mvip_ddim_cfg_step', ptr(e), int(cfg), ptr(scal), ptr(x), hw, ptr(unet_in),
          0 if unet_in is None else unet_in.shape[1], ptr(t_out), stream())
     return x
+
+
+# marching cubes (beyond the reference: mesh export, mvip_nerf_amd/mesh.py) -----------------------------
+
+def marching_cubes(grid, iso, bound_min, bound_max, tri_table):
+    """grid [nx, ny, nz] fp32 on the device -> (verts [V, 3] f32, faces [F, 3] int32, normals [V, 3] f32), csrc/mcubes.hip.
+    tri_table: the 256 x 16 int8 device table of mesh.py.  Reads back the two totals and the non-finite flag once (the
+    only synchronisation); raises ValueError for a non-finite grid, MvipError for more than 2^31 - 1 triangles."""
+    g = _f32c(grid)
+    nx, ny, nz = (int(s) for s in g.shape)
+    dev = g.device
+    G = _lib.load().mvip_mcubes_groups(nx, ny, nz)
+    if G < 0:
+        raise _lib.MvipError(f'marching_cubes: grid {tuple(g.shape)} outside 2..768 points per axis')
+    flags = torch.empty(nx * ny * nz, device=dev, dtype=torch.int16)
+    wg = torch.empty((G, 2), device=dev, dtype=torch.int64)
+    totals = torch.empty(3, device=dev, dtype=torch.int64)
+    call('mvip_mcubes_count', ptr(g), nx, ny, nz, float(iso), ptr(tri_table, torch.int8), ptr(flags, torch.int16),
+         ptr(wg, torch.int64), ptr(totals, torch.int64), stream())
+    n_verts, n_tris, nonfinite = (int(x) for x in totals.cpu())
+    if nonfinite:
+        raise ValueError('marching_cubes: the grid holds a non-finite value')
+    if n_tris > 2 ** 31 - 1:
+        raise _lib.MvipError(f'marching_cubes: {n_tris} triangles exceed int32 face indices')
+    verts = torch.empty((n_verts, 3), device=dev, dtype=_F32)
+    normals = torch.empty((n_verts, 3), device=dev, dtype=_F32)
+    faces = torch.empty((n_tris, 3), device=dev, dtype=torch.int32)
+    if n_verts or n_tris:
+        vid = torch.empty(nx * ny * nz, device=dev, dtype=torch.int32)
+        (x0, y0, z0), (x1, y1, z1) = ([float(v) for v in b] for b in (bound_min, bound_max))
+        call('mvip_mcubes_emit', ptr(g), nx, ny, nz, float(iso), x0, y0, z0, x1, y1, z1, ptr(tri_table, torch.int8),
+             ptr(flags, torch.int16), ptr(wg, torch.int64), n_verts, n_tris, ptr(vid, torch.int32), ptr(verts),
+             ptr(normals), ptr(faces, torch.int32), stream())
+    return verts, faces, normals

@@ -1,0 +1,87 @@
+"""Triangle mesh of a trained model: load a checkpoint in the reference's .tar format (what run.save_checkpoint writes,
+`module.` key prefixes accepted), sample sigma on a grid inside a box, run marching cubes, colour the vertices and write a
+binary PLY (mvip_nerf_amd/mesh.py).  Prints sigma percentiles of the grid (to choose --threshold) and each stage's time.
+
+  python tools/extract_mesh.py CKPT.tar --out mesh.ply [--model mlp|tcnn] [--bound-min x y z --bound-max x y z]
+         [--resolution 256] [--threshold 10] [--network fine|coarse] [--precision fp32|split] [--no-colors]
+"""
+import argparse
+import os
+import sys
+import time
+import types
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+from mvip_nerf_amd import mesh, run                                          # noqa: E402
+
+
+def model_args(n_importance):
+    """create_nerf / create_nerf_tcnn arguments of the reference's model (8x256 MLP, multires 10 / 4, view directions),
+    world-space rays (no NDC), nothing reloaded from a directory: the checkpoint is loaded here."""
+    return types.SimpleNamespace(
+        multires=10, i_embed=0, use_viewdirs=True, multires_views=4, N_importance=n_importance, alpha_model_path=None,
+        netdepth=8, netwidth=256, netdepth_fine=8, netwidth_fine=256, netchunk=65536, lrate=5e-4, basedir='.',
+        expname='', ft_path=None, no_reload=True, perturb=0., N_samples=64, white_bkgd=False, raw_noise_std=0.,
+        dataset_type='llff', no_ndc=True, lindisp=False, sigma_loss=False)
+
+
+def load_model(path, model, device):
+    ckpt = torch.load(path, map_location=device, weights_only=False)
+    fine = ckpt.get('network_fine_state_dict')
+    create = run.create_nerf if model == 'mlp' else run.create_nerf_tcnn
+    _, kw, _, _, _ = create(model_args(64 if fine is not None else 0), device=device)
+    kw['network_fn'].load_state_dict(run._strip_module_prefix(ckpt['network_fn_state_dict']))
+    if fine is not None:
+        kw['network_fine'].load_state_dict(run._strip_module_prefix(fine))
+    return kw, int(ckpt.get('global_step', 0))
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    ap.add_argument('ckpt')
+    ap.add_argument('--out', required=True)
+    ap.add_argument('--model', choices=('mlp', 'tcnn'), default='mlp')
+    ap.add_argument('--bound-min', type=float, nargs=3, default=(-1.0, -1.0, -1.0))
+    ap.add_argument('--bound-max', type=float, nargs=3, default=(1.0, 1.0, 1.0))
+    ap.add_argument('--resolution', type=int, nargs='+', default=[256], help='one count, or three')
+    ap.add_argument('--threshold', type=float, default=10.0)
+    ap.add_argument('--network', choices=('fine', 'coarse'), default='fine')
+    ap.add_argument('--precision', choices=('fp32', 'split'), default='fp32', help='MLP query precision (mlp model)')
+    ap.add_argument('--no-colors', action='store_true')
+    a = ap.parse_args(argv)
+    res = a.resolution[0] if len(a.resolution) == 1 else tuple(a.resolution)
+    dev = torch.device('cuda', 0)
+    kw, step = load_model(a.ckpt, a.model, dev)
+    if a.model == 'mlp':
+        for net in (kw['network_fn'], kw['network_fine']):
+            if net is not None:
+                net.inference_precision = 1 if a.precision == 'split' else 0
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return out, time.perf_counter() - t0
+
+    grid, t_grid = timed(lambda: mesh.density_grid(kw, a.bound_min, a.bound_max, res, a.network))
+    q = np.percentile(grid.float().cpu().numpy(), [1, 5, 25, 50, 75, 95, 99])
+    print(f'checkpoint {a.ckpt} (step {step}, model {a.model}, {a.network} network), grid {tuple(grid.shape)}')
+    print('sigma percentiles  ' + '  '.join(f'p{p}={v:.4g}' for p, v in zip((1, 5, 25, 50, 75, 95, 99), q)))
+    (verts, faces, normals), t_mc = timed(lambda: mesh.marching_cubes(grid, a.threshold, a.bound_min, a.bound_max))
+    colors, t_col = (None, 0.0) if a.no_colors else timed(lambda: mesh.vertex_colors(kw, verts, normals, a.network))
+    _, t_ply = timed(lambda: mesh.save_ply(a.out, mesh.Mesh(verts, faces, normals, colors)))
+    print(f'threshold {a.threshold}: {verts.shape[0]} vertices, {faces.shape[0]} triangles -> {a.out}')
+    print(f'time  density grid {t_grid * 1e3:.1f} ms  marching cubes {t_mc * 1e3:.1f} ms  colours {t_col * 1e3:.1f} ms  '
+          f'write {t_ply * 1e3:.1f} ms')
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())
