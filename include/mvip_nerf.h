@@ -140,6 +140,22 @@ int mvip_mlp_forward_rays16(const float *packed16, const float *rows, const floa
 int mvip_mlp_forward_points16(const float *packed16, const float *pts, const float *dirs, int64_t P,
                               float *raw, void *stream);
 
+/* Folded inference image (ops.mlp_pack16 / NeRF.packed_w16, NeRF.fold_feature_inference): feature_linear has no
+ * activation, so a no-grad forward evaluates the view layer as relu(W' h + Wv[:, 256:] e_dir + b') with
+ * W' = Wv[:, :256] Wf and b' = Wv[:, :256] bf + bv and skips the feature layer (11 % of the matrix work).  sigma is
+ * bit-identical to the unfolded entries, rgb equal to rounding.
+ * mvip_mlp_packed_fold_floats(): size of the EXTENDED image = [the mvip_mlp_pack16 image, unchanged | folded view blocks |
+ *   a copy of the small-vector section carrying b'].  Its head drives every entry that takes a plain packed16.
+ * mvip_mlp_fold_pack16(): fills the tail of an extended image whose head mvip_mlp_pack16 has written on the same
+ *   stream; W' and b' are accumulated in fp64 in a fixed order and rounded once (deterministic, identical on every rank).
+ * mvip_*_fold: the four inference launches on an extended image; arguments as their unfolded twins. */
+int64_t mvip_mlp_packed_fold_floats(void);
+int mvip_mlp_fold_pack16(const float *const *params_host, float *packed16_ext, void *stream);
+int mvip_mlp_forward_rays16_fold(const float *packed16_ext, const float *rows, const float *z, int64_t B, int S,
+                                 float *raw, void *stream);
+int mvip_mlp_forward_points16_fold(const float *packed16_ext, const float *pts, const float *dirs, int64_t P,
+                                   float *raw, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * a10 (row g)  render_rays as TWO launches per chunk (DS_NeRF/run.py:1703-1847), no-grad renders of the native 8x256
  * networks with 64 coarse + <= 64 fine samples: the same device functions as the stand-alone entry points, fused behind
@@ -159,6 +175,15 @@ int mvip_render_coarse_fused(const float *packed16, const float *rows, int64_t B
 int mvip_render_fine_fused(const float *packed16, const float *rows, const float *z, int64_t B, const float *noise,
                            int flags, float *raw, float *rgb, float *disp, float *acc, float *depth, float *weights,
                            float *alpha, void *stream);
+/* the same two launches with the folded network (run.py render_rays when NeRF.fold_feature_inference); packed16_ext is an
+ * extended image with its tail filled (mvip_mlp_fold_pack16) */
+int mvip_render_coarse_fused_fold(const float *packed16_ext, const float *rows, int64_t B, const float *t_vals, int lindisp,
+                                  const float *t_rand, const float *noise, const float *u, int u_is_row, int Nf, int flags,
+                                  float *rgb0, float *disp0, float *acc0, float *depth0, float *weights0, float *alpha0,
+                                  float *z_merged, float *z_std, void *stream);
+int mvip_render_fine_fused_fold(const float *packed16_ext, const float *rows, const float *z, int64_t B, const float *noise,
+                                int flags, float *raw, float *rgb, float *disp, float *acc, float *depth, float *weights,
+                                float *alpha, void *stream);
 
 /* Backward: d_raw [P,4] -> the 24 parameter gradients.  grads_host is a HOST array of 24 device
  * pointers (state-dict order, natural [out][in] shapes) that are ACCUMULATED into with fp32

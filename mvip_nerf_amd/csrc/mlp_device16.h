@@ -58,12 +58,14 @@ __device__ __forceinline__ void glds(const float *src_lane, float *dst_wave) {
 // NSLOT = ring slots of 16 KB.  WRAP (the persistent kernel, mlp_fwd16.hip): chunk indices past the end of the image wrap to
 // the start, i.e. the NEXT tile's first chunks are staged while this tile's last layers run; TOTAL_CHUNKS % NSLOT == 0 keeps the
 // slot of a chunk a compile-time function of its index across tiles.
-template <int NSLOT = NSLOT16, bool WRAP = false>
+// FOLD (the folded inference image, mlp_layout.h): chunks from FOLD_FIRST_CHUNK on are the folded view blocks in the tail of
+// the extended image -- one wave-uniform base select; the stream ends after FOLD_TOTAL_CHUNKS chunks.
+template <int NSLOT = NSLOT16, bool WRAP = false, bool FOLD = false>
 struct Stream16T {
     const float *packed;
     float *lds;
     int wave, lane;
-    int total_chunks = TOTAL_CHUNKS;     // chunks in the image being streamed (the transposed image has more)
+    int total_chunks = FOLD ? FOLD_TOTAL_CHUNKS : TOTAL_CHUNKS;     // chunks in the image being streamed (the transposed image has more)
     lds_cfloat *lds_read = nullptr;      // WRAP: operand reads go through this LDS pointer (the persistent kernel makes it opaque per tile)
     static constexpr int nslot = NSLOT;
     static constexpr bool wrap = WRAP;
@@ -72,6 +74,7 @@ struct Stream16T {
         if (WRAP && g >= total_chunks) g -= total_chunks;
         if (g < total_chunks) {
             const float *src = packed + (int64_t)g * CHUNK_FLOATS + wave * 512 + lane * 4;
+            if constexpr (FOLD) { if (g >= FOLD_FIRST_CHUNK) src += FOLD_TAIL_A - FOLD_FIRST_CHUNK * CHUNK_FLOATS; }
             float *dst = lds + slot * CHUNK_FLOATS + wave * 512;
             glds<0>(src, dst);
             glds<1024>(src, dst);

@@ -74,6 +74,22 @@ static_assert(SB_BRGB + 4 <= SEC_B_FLOATS, "section B overflow");
 
 constexpr int PACKED_FLOATS = SEC_A_FLOATS + SEC_B_FLOATS;  // 597,248
 
+// Folded inference image of the 16-point kernels (mlp_fwd16.hip, FOLD): feature_linear has no activation, so
+//     views_linears.0(cat[feature_linear(h), e_dir]) = [Wv[:, :256] Wf | Wv[:, 256:]] cat[h, e_dir] + (Wv[:, :256] bf + bv)
+// and a no-grad forward can skip the feature layer.  The extended image is
+//     [ the plain image, PACKED_FLOATS floats, unchanged | FOLD_BLOCKS folded view blocks, whole chunks | a section-B copy ]
+// where the section-B copy additionally carries the folded bias b' at SB_BFOLD (unused tail of section B).  The folded
+// stream is the plain stream up to OFF_FEAT followed by the folded view blocks: FOLD_TOTAL_CHUNKS chunks.
+constexpr int FOLD_BLOCKS = LV_BLOCKS;                                  // 144: same shape as the view layer
+constexpr int FOLD_FIRST_CHUNK = OFF_FEAT / CHUNK_BLOCKS;               // 120: first chunk taken from the tail
+constexpr int FOLD_TOTAL_CHUNKS = FOLD_FIRST_CHUNK + FOLD_BLOCKS / CHUNK_BLOCKS;   // 129
+static_assert(OFF_FEAT % CHUNK_BLOCKS == 0 && FOLD_BLOCKS % CHUNK_BLOCKS == 0, "folded stream must be whole chunks");
+constexpr int SB_BFOLD = SB_BRGB + 4;                                   // 3080: b', 128 floats
+static_assert(SB_BFOLD % 4 == 0 && SB_BFOLD + 128 <= SEC_B_FLOATS, "folded bias must fit in section B");
+constexpr int FOLD_TAIL_A = PACKED_FLOATS;                              // folded blocks
+constexpr int FOLD_TAIL_B = FOLD_TAIL_A + FOLD_BLOCKS * BLOCK_FLOATS;   // section-B copy with b'
+constexpr int PACKED_FOLD_FLOATS = FOLD_TAIL_B + SEC_B_FLOATS;          // 637,440
+
 // state-dict order of the 24 parameter tensors
 enum Param {
     P_W0 = 0, P_B0 = 1,            // pts_linears.i.weight / bias at 2i, 2i+1

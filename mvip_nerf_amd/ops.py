@@ -121,12 +121,52 @@ def mlp_pack(params):
     return packed
 
 
-def mlp_pack16(params, packed_f32):
-    """Image for the two-waves-per-SIMD inference kernel (16 points per wave, csrc/mlp_fwd16.hip)."""
+_PACKED_FOLD_FLOATS = None
+
+
+def packed_fold_floats():
+    global _PACKED_FOLD_FLOATS
+    if _PACKED_FOLD_FLOATS is None:
+        _PACKED_FOLD_FLOATS = int(_lib.load().mvip_mlp_packed_fold_floats())
+    return _PACKED_FOLD_FLOATS
+
+
+def mlp_pack16(params, packed_f32, fold=True):
+    """Image for the two-waves-per-SIMD kernels (16 points per wave, csrc/mlp_fwd16.hip): the EXTENDED image
+    [plain image, packed_floats() | folded view blocks | small vectors with the folded bias] (csrc/mlp_layout.h).  Handed to
+    mlp_rays / mlp_points / render_*_fused it selects the folded inference network (feature_linear multiplied into the view
+    layer); its head, plain16(img), selects the unfolded one and is what the training forward reads.  fold=False leaves
+    the tail unwritten -- mlp_fold_pack16 fills it later -- and such an image must reach the kernels only as plain16(img)."""
     ps = [_f32c(p.detach()) for p in params]
-    img = torch.empty(packed_floats(), device=ps[0].device, dtype=_F32)
+    img = torch.empty(packed_fold_floats(), device=ps[0].device, dtype=_F32)
     call('mvip_mlp_pack16', _lib.ptr_array(ps), ptr(packed_f32), ptr(img), stream())
+    if fold:
+        call('mvip_mlp_fold_pack16', _lib.ptr_array(ps), ptr(img), stream())
     return img
+
+
+def mlp_fold_pack16(params, img):
+    """Fill the tail of an extended image whose head mlp_pack16 wrote for the same parameters."""
+    if img.numel() != packed_fold_floats():
+        raise _lib.MvipError('mlp_fold_pack16 needs the extended image of mlp_pack16')
+    ps = [_f32c(p.detach()) for p in params]
+    call('mvip_mlp_fold_pack16', _lib.ptr_array(ps), ptr(img), stream())
+    return img
+
+
+def plain16(img):
+    """The plain (unfolded) image inside an image of mlp_pack16: a view of its first packed_floats() floats."""
+    return img[:packed_floats()]
+
+
+def _fold16(packed16):
+    """'_fold' when `packed16` is an extended image (the folded entries run), '' for a plain one."""
+    n = packed16.numel()
+    if n == packed_fold_floats():
+        return '_fold'
+    if n != packed_floats():
+        raise _lib.MvipError(f'not an image of mlp_pack16: {n} floats')
+    return ''
 
 
 def mlp_pack_f16x3(params, packed_f32):
@@ -338,7 +378,7 @@ def mlp_rays(rows, z, packed, params, packed_f16x3=None, train_f16x3=None, packe
     elif packed_f16x3 is not None:
         call('mvip_mlp_forward_rays', ptr(packed_f16x3), ptr(rows), ptr(z), B, S, ptr(raw), 1, stream())
     elif packed16 is not None:
-        call('mvip_mlp_forward_rays16', ptr(packed16), ptr(rows), ptr(z), B, S, ptr(raw), stream())
+        call('mvip_mlp_forward_rays16' + _fold16(packed16), ptr(packed16), ptr(rows), ptr(z), B, S, ptr(raw), stream())
     else:
         call('mvip_mlp_forward_rays', ptr(packed), ptr(rows), ptr(z), B, S, ptr(raw), 0, stream())
     return raw
@@ -356,7 +396,7 @@ def mlp_points(pts, dirs, packed, params, packed_f16x3=None, train_f16x3=None, p
     elif packed_f16x3 is not None:
         call('mvip_mlp_forward_points', ptr(packed_f16x3), ptr(pts), ptr(dirs), pts.shape[0], ptr(raw), 1, stream())
     elif packed16 is not None:
-        call('mvip_mlp_forward_points16', ptr(packed16), ptr(pts), ptr(dirs), pts.shape[0], ptr(raw), stream())
+        call('mvip_mlp_forward_points16' + _fold16(packed16), ptr(packed16), ptr(pts), ptr(dirs), pts.shape[0], ptr(raw), stream())
     else:
         call('mvip_mlp_forward_points', ptr(packed), ptr(pts), ptr(dirs), pts.shape[0], ptr(raw), 0, stream())
     return raw
@@ -1654,7 +1694,7 @@ def render_coarse_fused(packed16, rows, lindisp, t_rand, noise, u, white_bkgd, n
     zstd = torch.empty((B,), device=dev, dtype=_F32)
     tr = None if t_rand is None else _f32c(t_rand)
     nz = None if noise is None else _f32c(noise)
-    call('mvip_render_coarse_fused', ptr(packed16), ptr(rows), B, ptr(_t_vals(64, dev)), int(bool(lindisp)), ptr(tr), ptr(nz),
+    call('mvip_render_coarse_fused' + _fold16(packed16), ptr(packed16), ptr(rows), B, ptr(_t_vals(64, dev)), int(bool(lindisp)), ptr(tr), ptr(nz),
          ptr(u), int(u.dim() == 1), int(Nf), COMP_WHITE if white_bkgd else 0, ptr(rgb), ptr(disp), ptr(acc), ptr(None),
          ptr(None), ptr(alpha), ptr(zm), ptr(zstd), stream())
     return rgb, disp, acc, alpha, zm, zstd
@@ -1673,7 +1713,7 @@ def render_fine_fused(packed16, rows, z, noise, white_bkgd, need_alpha=False, wa
     alpha = torch.empty((B, 128), device=dev, dtype=_F32) if need_alpha else None
     raw = torch.empty((B, 128, 4), device=dev, dtype=_F32) if want_raw else None
     nz = None if noise is None else _f32c(noise)
-    call('mvip_render_fine_fused', ptr(packed16), ptr(rows), ptr(z), B, ptr(nz), COMP_WHITE if white_bkgd else 0, ptr(raw),
+    call('mvip_render_fine_fused' + _fold16(packed16), ptr(packed16), ptr(rows), ptr(z), B, ptr(nz), COMP_WHITE if white_bkgd else 0, ptr(raw),
          ptr(rgb), ptr(disp), ptr(acc), ptr(depth), ptr(weights), ptr(alpha), stream())
     return rgb, disp, acc, weights, depth, alpha, raw
 

@@ -73,11 +73,15 @@ class NeRF(nn.Module):
         self._packed16_key = None
         self._packed_w16 = None
         self._packed_w16_key = None
+        self._packed_w16_folded = False
         self._packed_hw16 = None
         self._packed_hw16_key = None
         self.two_wave_f16x3 = True        # no-grad split-precision forwards use csrc/mlp_fwd16_f16x3.hip (two waves per SIMD)
         self.two_wave_inference = True    # no-grad fp32 forwards use csrc/mlp_fwd16.hip (two waves per SIMD)
         self.two_wave_training = True     # ... and so does the stash-writing fp32 training forward from ray rows
+        # no-grad fp32 forwards on the two-wave kernel multiply feature_linear into the view layer (W' = Wv[:, :256] Wf, formed
+        # once per weight version): 11 % less matrix work, sigma bit-identical, rgb equal to rounding.  False: the unfolded launches.
+        self.fold_feature_inference = True
         # 0: exact fp32 MFMA.  1: split-precision fp16 MFMA ("f16x3", ~1e-6 relative, fp32 accumulate).
         self.inference_precision = 0  # forward passes that need no gradient (rendering)
         self.train_precision = 0      # stash-writing forward, delta and weight-gradient kernels
@@ -96,6 +100,7 @@ class NeRF(nn.Module):
         self._packed = self._packed_key = None
         self._packed16 = self._packed16_key = None
         self._packed_w16 = self._packed_w16_key = None
+        self._packed_w16_folded = False
         self._packed_hw16 = self._packed_hw16_key = None
 
     def load_state_dict(self, *args, **kwargs):
@@ -134,13 +139,24 @@ class NeRF(nn.Module):
             self._packed16_key = self._packed_key
         return self._packed16
 
-    def packed_w16(self):
-        """Image of the two-waves-per-SIMD exact-fp32 inference kernel (csrc/mlp_fwd16.hip)."""
+    def _w16(self, fold):
+        """The extended image of ops.mlp_pack16, one per weight version.  Its folded tail is filled on the first call of that
+        version that asks for it: a training-only iteration (_train16) never launches the fold pack."""
         packed = self.packed()
         if self._packed_w16 is None or self._packed_w16_key != self._packed_key:
-            self._packed_w16 = ops.mlp_pack16(self.param_list(), packed)
+            self._packed_w16 = ops.mlp_pack16(self.param_list(), packed, fold=False)
             self._packed_w16_key = self._packed_key
+            self._packed_w16_folded = False
+        if fold and not self._packed_w16_folded:
+            ops.mlp_fold_pack16(self.param_list(), self._packed_w16)
+            self._packed_w16_folded = True
         return self._packed_w16
+
+    def packed_w16(self):
+        """Image of the two-waves-per-SIMD exact-fp32 inference kernel (csrc/mlp_fwd16.hip): the extended image (folded
+        network) when fold_feature_inference, else the plain image inside it (unfolded network)."""
+        img = self._w16(self.fold_feature_inference)
+        return img if self.fold_feature_inference else ops.plain16(img)
 
     def packed_f16x3_w16(self):
         """Image of the two-waves-per-SIMD split-precision inference kernel (csrc/mlp_fwd16_f16x3.hip)."""
@@ -156,7 +172,7 @@ class NeRF(nn.Module):
 
     def _train16(self):
         grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
-        return self.packed_w16() if (self.two_wave_training and grad and self.train_precision == 0) else None
+        return ops.plain16(self._w16(False)) if (self.two_wave_training and grad and self.train_precision == 0) else None
 
     def _fast_image(self):
         return self.packed_f16x3() if self.inference_precision == 1 else None
