@@ -705,6 +705,47 @@ int mvip_mcubes_emit(const float *grid, int nx, int ny, int nz, float iso, float
                      float y1, float z1, const void *tri_table, const void *flags, const int64_t *wg, int64_t n_verts,
                      int64_t n_tris, int *vid, float *verts, float *normals, int *faces, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Occupancy-grid empty-space skipping for no-grad renders (beyond the reference: it evaluates every
+ * sample; csrc/occupancy.hip, mvip_nerf_amd/occupancy.py).  A grid is a box cut into cells = (cx,cy,cz),
+ * 1 <= c <= 512 per axis, one bit per cell: linear cell l = (ix*cy + iy)*cz + iz (z fastest), bit l & 31
+ * of int32 word l >> 5, (cx*cy*cz + 31) / 32 words in DEVICE memory, unused tail bits zero.  Entry points
+ * that test points take the grid as box = {bmin[3], inv[3]} (6 floats, HOST memory; inv = cells /
+ * (bmax - bmin) > 0, rounded to fp32 by the caller), cells (3 ints, HOST memory) and words.  Cell of a
+ * point p, per axis in fp32: f = floorf((p - bmin) * inv); p is inside the box iff 0 <= f < c on all
+ * three axes (NaN / infinite coordinates: outside); keep(p) = outside the box, or bit set.
+ *
+ * mvip_occupancy_build: sigma [cx*k+1, cy*k+1, cz*k+1] fp32 (k = samples_per_cell, 1..8; z fastest) ->
+ *   words: cell (i,j,l) owns points i*k .. (i+1)*k on each axis and is occupied iff any of them has
+ *   !(sigma <= threshold) (NaN counts as occupied); threshold >= 0, finite.
+ * mvip_occupancy_dilate: words_out = OR over the <= 27 cells at Chebyshev distance <= 1 of words_in
+ *   (clipped at the faces); the two arrays must differ.
+ * mvip_occupancy_groups: G, the workgroup count of a chunk of B rays x S samples (-1 when S < 1 or
+ *   B*S exceeds 2^31 - 1).
+ * mvip_occupancy_count: rows [B,11], z [B,S]; flat sample s = ray*S + j has the point
+ *   rows[0:3] + rows[3:6] * z (the expression of the mvip_mlp_forward_rays* kernels).  wg [G] int32
+ *   receives the exclusive offsets of the kept samples of each workgroup, total [1] int64 their number
+ *   K; the caller reads total back once to allocate mvip_occupancy_emit's outputs.  Optional (NULL to
+ *   skip): mask [B,S] uint8 = keep, pts_full [B,S,3].  B == 0: MVIP_OK, nothing launched or written.
+ * mvip_occupancy_emit: from count's wg and K: in ascending s, idx [K] int32 = s, pts [K,3] the sample
+ *   points, dirs [K,3] = rows[8:11].  B == 0 or K == 0: MVIP_OK, nothing launched.
+ * mvip_scatter_raw: raw [n,4] = 0, then raw[idx[j]] = raw_k[j] for j < K (idx ascending, distinct, < n;
+ *   K <= n <= 2^31 - 1; raw and raw_k 16-byte aligned).  The zero fill is part of the operation (K == 0
+ *   fills only); n == 0: MVIP_OK, nothing launched.
+ * mvip_occupancy_lookup: out [P] uint8 = keep(pts[p]), pts [P,3].  P == 0: MVIP_OK, nothing launched.
+ * No atomics anywhere: the outputs are reproducible bit for bit. */
+int mvip_occupancy_build(const float *sigma, int cx, int cy, int cz, int samples_per_cell, float threshold, int *words,
+                         void *stream);
+int mvip_occupancy_dilate(const int *words_in, int cx, int cy, int cz, int *words_out, void *stream);
+int64_t mvip_occupancy_groups(int64_t B, int S);
+int mvip_occupancy_count(const float *rows, const float *z, int64_t B, int S, const float *box, const int *cells,
+                         const int *words, int *wg, int64_t *total, void *mask, float *pts_full, void *stream);
+int mvip_occupancy_emit(const float *rows, const float *z, int64_t B, int S, const float *box, const int *cells,
+                        const int *words, const int *wg, int64_t K, int *idx, float *pts, float *dirs, void *stream);
+int mvip_scatter_raw(const float *raw_k, const int *idx, int64_t K, int64_t n, float *raw, void *stream);
+int mvip_occupancy_lookup(const float *pts, int64_t P, const float *box, const int *cells, const int *words, void *out,
+                          void *stream);
+
 #ifdef __cplusplus
 }
 #endif

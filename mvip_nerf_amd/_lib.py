@@ -164,6 +164,15 @@ _SIGNATURES = {
     'mvip_mcubes_count': (_int, [_c_f, _int, _int, _int, _flt, _c_f, _c_f, _c_f, _c_f, _c_f]),
     'mvip_mcubes_emit': (_int, [_c_f, _int, _int, _int, _flt, _flt, _flt, _flt, _flt, _flt, _flt, _c_f, _c_f, _c_f, _i64, _i64,
                                 _c_f, _c_f, _c_f, _c_f, _c_f]),
+    'mvip_occupancy_build': (_int, [_c_f, _int, _int, _int, _int, _flt, _c_f, _c_f]),
+    'mvip_occupancy_dilate': (_int, [_c_f, _int, _int, _int, _c_f, _c_f]),
+    'mvip_occupancy_groups': (_i64, [_i64, _int]),
+    'mvip_occupancy_count': (_int, [_c_f, _c_f, _i64, _int, ctypes.POINTER(_flt), ctypes.POINTER(_int), _c_f, _c_f, _c_f, _c_f,
+                                    _c_f, _c_f]),
+    'mvip_occupancy_emit': (_int, [_c_f, _c_f, _i64, _int, ctypes.POINTER(_flt), ctypes.POINTER(_int), _c_f, _c_f, _i64, _c_f,
+                                   _c_f, _c_f, _c_f]),
+    'mvip_scatter_raw': (_int, [_c_f, _c_f, _i64, _i64, _c_f, _c_f]),
+    'mvip_occupancy_lookup': (_int, [_c_f, _i64, ctypes.POINTER(_flt), ctypes.POINTER(_int), _c_f, _c_f, _c_f]),
 }
 
 # every symbol include/mvip_nerf.h declares; tests check the built library exports all of them

@@ -1805,3 +1805,98 @@ def marching_cubes(grid, iso, bound_min, bound_max, tri_table):
              ptr(flags, torch.int16), ptr(wg, torch.int64), n_verts, n_tris, ptr(vid, torch.int32), ptr(verts),
              ptr(normals), ptr(faces, torch.int32), stream())
     return verts, faces, normals
+
+
+# occupancy-grid empty-space skipping (beyond the reference, mvip_nerf_amd/occupancy.py, csrc/occupancy.hip) -------------
+
+_I32 = torch.int32
+
+
+def _occ_args(box, cells):
+    """The grid's host-side arguments: box = (bmin[3], inv[3]) as six C floats, cells as three C ints."""
+    import ctypes
+    return (ctypes.c_float * 6)(*[float(v) for v in box]), (ctypes.c_int * 3)(*[int(c) for c in cells])
+
+
+def occupancy_words(cells):
+    """Number of int32 words of a grid of `cells` = (cx, cy, cz): one bit per cell, z fastest."""
+    cx, cy, cz = (int(c) for c in cells)
+    return (cx * cy * cz + 31) // 32
+
+
+def occupancy_build(sigma, cells, samples_per_cell, threshold):
+    """sigma [cx k + 1, cy k + 1, cz k + 1] fp32 on the device -> int32 words: a cell is occupied iff any of the
+    (k + 1)^3 points it owns has !(sigma <= threshold)."""
+    s = _f32c(sigma)
+    cx, cy, cz = (int(c) for c in cells)
+    k = int(samples_per_cell)
+    if tuple(s.shape) != (cx * k + 1, cy * k + 1, cz * k + 1):
+        raise _lib.MvipError(f'occupancy_build: sigma {tuple(s.shape)} for cells {(cx, cy, cz)} x {k} samples per cell')
+    words = torch.empty(occupancy_words(cells), device=s.device, dtype=_I32)
+    call('mvip_occupancy_build', ptr(s), cx, cy, cz, int(samples_per_cell), float(threshold), ptr(words, _I32), stream())
+    return words
+
+
+def occupancy_dilate(words, cells):
+    """One round of 27-neighbour dilation (clipped at the faces): a new word tensor."""
+    cx, cy, cz = (int(c) for c in cells)
+    if tuple(words.shape) != (occupancy_words(cells),):
+        raise _lib.MvipError(f'occupancy_dilate: {tuple(words.shape)} words for cells {(cx, cy, cz)}')
+    out = torch.empty_like(words)
+    call('mvip_occupancy_dilate', ptr(words, _I32), cx, cy, cz, ptr(out, _I32), stream())
+    return out
+
+
+def occupancy_compact(rows, z, box, cells, words, want_mask=False, want_pts=False):
+    """The kept samples of a ray chunk, in ascending flat order s = ray * S + j: (idx int32 [K], pts [K, 3], dirs [K, 3],
+    K, mask uint8 [B, S] | None, pts_full [B, S, 3] | None).  rows [B, 11], z [B, S]; box = (bmin, inv) six floats, cells
+    three ints (host), words on the rows' device.  Reads K back once (the only synchronisation)."""
+    rows, z = _f32c(rows), _f32c(z)
+    B, S = z.shape
+    dev = z.device
+    if tuple(rows.shape) != (B, 11) or tuple(words.shape) != (occupancy_words(cells),):
+        raise _lib.MvipError(f'occupancy_compact: rows {tuple(rows.shape)}, z {tuple(z.shape)}, {tuple(words.shape)} words '
+                             f'for cells {tuple(cells)}')
+    cbox, ccells = _occ_args(box, cells)
+    G = _lib.load().mvip_occupancy_groups(B, S)
+    if G < 0:
+        raise _lib.MvipError(f'occupancy_compact: {B} x {S} samples exceed int32 sample indices')
+    mask = torch.empty((B, S), device=dev, dtype=torch.uint8) if want_mask else None
+    full = torch.empty((B, S, 3), device=dev, dtype=_F32) if want_pts else None
+    K = 0
+    if B > 0:
+        wg = torch.empty(G, device=dev, dtype=_I32)
+        total = torch.empty(1, device=dev, dtype=torch.int64)
+        call('mvip_occupancy_count', ptr(rows), ptr(z), B, S, cbox, ccells, ptr(words, _I32), ptr(wg, _I32),
+             ptr(total, torch.int64), ptr(mask, torch.uint8), ptr(full), stream())
+        K = int(total.cpu())
+    idx = torch.empty(K, device=dev, dtype=_I32)
+    pts = torch.empty((K, 3), device=dev, dtype=_F32)
+    dirs = torch.empty((K, 3), device=dev, dtype=_F32)
+    if K > 0:
+        call('mvip_occupancy_emit', ptr(rows), ptr(z), B, S, cbox, ccells, ptr(words, _I32), ptr(wg, _I32), K,
+             ptr(idx, _I32), ptr(pts), ptr(dirs), stream())
+    return idx, pts, dirs, K, mask, full
+
+
+def scatter_raw(raw_k, idx, shape):
+    """raw [*shape, 4] fp32: raw_k [K, 4] at the flat samples idx [K], zeros elsewhere (the zero fill is part of the op)."""
+    n = _numel(shape)
+    K = int(idx.shape[0])
+    raw_k = _f32c(raw_k)
+    if tuple(raw_k.shape) != (K, 4):
+        raise _lib.MvipError(f'scatter_raw: raw_k {tuple(raw_k.shape)} for {K} indices (4 channels expected)')
+    raw = torch.empty(tuple(shape) + (4,), device=idx.device, dtype=_F32)
+    call('mvip_scatter_raw', ptr(raw_k) if K else ptr(None), ptr(idx, _I32) if K else ptr(None), K, n, ptr(raw), stream())
+    return raw
+
+
+def occupancy_lookup(pts, box, cells, words):
+    """keep(p) of pts [P, 3]: uint8 [P], 1 = outside the box or in an occupied cell."""
+    p = _f32c(pts.reshape(-1, 3))
+    if tuple(words.shape) != (occupancy_words(cells),):
+        raise _lib.MvipError(f'occupancy_lookup: {tuple(words.shape)} words for cells {tuple(cells)}')
+    out = torch.empty(p.shape[0], device=p.device, dtype=torch.uint8)
+    cbox, ccells = _occ_args(box, cells)
+    call('mvip_occupancy_lookup', ptr(p), p.shape[0], cbox, ccells, ptr(words, _I32), ptr(out, torch.uint8), stream())
+    return out

@@ -169,7 +169,7 @@ FUSED_RENDER_MAX_RAYS = int(os.environ.get('MVIP_FUSED_RENDER_MAX_RAYS', '4096')
 
 def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False, lindisp=False, perturb=0.,
                 N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0., pytest=False,
-                sigma_loss=None, verbose=False, need_alpha=False, detach_weights=False, coarse_grad=True):
+                sigma_loss=None, verbose=False, need_alpha=False, detach_weights=False, coarse_grad=True, occupancy=None):
     """DS_NeRF/run.py:1703-1847: stratified depths -> coarse MLP -> compositing -> inverse-CDF
     resampling + merge -> fine MLP -> compositing.  Five kernel launches per chunk on the native
     path (z, MLP, composite, sample+merge, MLP, composite) instead of ~150 torch ops.
@@ -178,7 +178,11 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
     the coarse network only through the DETACHED resampled depths (run.py:1812), so a caller that uses only
     rgb_map / disp_map / depth_map / acc_map of a render (the masked set, the normal frame, the neighbour views of
     run.py:919-974) gets exactly zero gradient from it into the coarse network; coarse_grad=False runs that pass
-    without autograd (no activation stash, no backward: a third of the points), changing no value and no gradient."""
+    without autograd (no activation stash, no backward: a third of the points), changing no value and no gradient.
+
+    `occupancy` (extension, default None = every path as it is without it): an occupancy.OccupancyGrid; no-grad renders
+    only.  The render is the one this chain would produce if the network's raw output were zero at every sample whose
+    point lies in a cell the grid marks empty, and the network is not evaluated there (_render_rays_occupancy)."""
     ray_batch = ray_batch.float() if ray_batch.dtype != torch.float32 else ray_batch
     ray_batch = ray_batch.contiguous()
     N_rays, ncols = ray_batch.shape
@@ -207,6 +211,10 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
     coarse_net = network_fn if network_fn is not None else (
         network_fine.alpha_model if getattr(network_fine, 'alpha_model', None) is not None else network_fine)
     fine_net = network_fn if network_fine is None else network_fine
+    if occupancy is not None:
+        return _render_rays_occupancy(occupancy, rows, ncols, coarse_net, fine_net, network_query_fn, N_samples, retraw,
+                                      lindisp, perturb, N_importance, white_bkgd, raw_noise_std, pytest, sigma_loss,
+                                      need_alpha, detach_weights, t_rand)
     if (FUSED_RENDER and not torch.is_grad_enabled() and 0 < N_rays <= FUSED_RENDER_MAX_RAYS and N_samples == 64 and 0 < N_importance <= 64
             and ncols == 11 and sigma_loss is None and getattr(network_query_fn, '_mvip_native', False)
             and isinstance(coarse_net, NeRF) and isinstance(fine_net, NeRF)):
@@ -268,6 +276,73 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
         for k in ret:
             if torch.isnan(ret[k]).any() or torch.isinf(ret[k]).any():
                 print(f"! [Numerical Error] {k} contains nan or inf.")
+    return ret
+
+
+def _render_rays_occupancy(grid, rows, ncols, coarse_net, fine_net, network_query_fn, N_samples, retraw, lindisp, perturb,
+                           N_importance, white_bkgd, raw_noise_std, pytest, sigma_loss, need_alpha, detach_weights, t_rand):
+    """render_rays with an occupancy grid: per pass, compact the samples the grid keeps (ops.occupancy_compact: outside the
+    box, or in an occupied cell), query the network at those points only, scatter the result into a zero raw tensor and
+    composite as usual; the fine depths come from the masked coarse weights.  Takes precedence over the two-launch fused
+    path.  A pass that keeps nothing launches no network kernel.  grid.stats counts samples, kept samples and network
+    launches.  Refused (ValueError): autograd with a parameter that requires grad (skipping has no backward),
+    raw_noise_std > 0 (the noise is added to sigma before the relu: an empty sample would not stay empty), sigma_loss, a
+    grid on another device than the rays, ray rows without view directions."""
+    from .occupancy import OccupancyGrid
+    if not isinstance(grid, OccupancyGrid):
+        raise ValueError(f'occupancy must be an occupancy.OccupancyGrid, got {type(grid).__name__}')
+    if raw_noise_std > 0.:
+        raise ValueError('occupancy: raw_noise_std > 0 adds noise to sigma before the relu, so a sample in an empty cell '
+                         'would not stay empty; render with raw_noise_std = 0')
+    if sigma_loss is not None:
+        raise ValueError('occupancy: sigma_loss is a training loss; skipping is for no-grad renders only')
+    nets = [coarse_net] + ([fine_net] if N_importance > 0 else [])
+    if torch.is_grad_enabled() and any(p.requires_grad for net in nets for p in net.parameters()):
+        raise ValueError('occupancy: skipping has no backward; render under torch.no_grad() (or freeze the parameters)')
+    if ncols != 11:
+        raise ValueError(f'occupancy: ray rows of 11 columns (with view directions, no depth column) expected, got {ncols}')
+    if grid.words.device != rows.device:
+        raise ValueError(f'occupancy: the grid is on {grid.words.device}, the rays on {rows.device}; use grid.to(device)')
+    N_rays, dev = rows.shape[0], rows.device
+    box, cells, words = grid.box(), grid.cells, grid.words
+    native = getattr(network_query_fn, '_mvip_native', False)
+
+    def query(z, net, which):
+        idx, pts, dirs, K, _, _ = ops.occupancy_compact(rows, z, box, cells, words)
+        grid.stats['samples_' + which] += z.numel()
+        grid.stats['kept_' + which] += K
+        if K > 0:
+            grid.stats['network_launches'] += 1
+            if native and isinstance(net, NeRF):
+                raw_k = net.query_points(pts, dirs)
+            else:
+                raw_k = network_query_fn(pts[:, None, :], dirs, net).reshape(K, -1)
+        else:
+            raw_k = rows.new_empty((0, 4))
+        if raw_k.shape[-1] != 4:
+            raise ValueError(f'occupancy: the network returns {raw_k.shape[-1]} channels per sample, 4 expected')
+        return ops.scatter_raw(raw_k, idx, tuple(z.shape))
+
+    z_vals = ops.stratified_z(rows, N_samples, lindisp, t_rand)
+    raw = query(z_vals, coarse_net, 'coarse')
+    rgb_map, disp_map, acc_map, weights, depth_map, alpha = ops.composite(raw, z_vals, rows, None, white_bkgd,
+                                                                          detach_weights, need_alpha)
+    if N_importance > 0:
+        rgb_map_0, disp_map_0, acc_map_0, alpha0 = rgb_map, disp_map, acc_map, alpha
+        u = _uniforms((N_rays,), N_importance, perturb == 0., pytest, dev)
+        _, z_vals, z_std, _, _ = ops.sample_pdf_merge(z_vals, weights, u)
+        raw = query(z_vals, fine_net, 'fine')
+        rgb_map, disp_map, acc_map, weights, depth_map, alpha = ops.composite(raw, z_vals, rows, None, white_bkgd,
+                                                                              detach_weights, need_alpha)
+    ret = {'rgb_map': rgb_map, 'disp_map': disp_map, 'acc_map': acc_map, 'depth_map': depth_map,
+           'weights': weights, 'z_vals': z_vals}
+    if retraw:
+        ret['raw'] = raw
+    if need_alpha:
+        ret['alpha'] = alpha
+        ret['alpha0'] = alpha0          # NameError without N_importance, like render_rays
+    if N_importance > 0:
+        ret['rgb0'], ret['disp0'], ret['acc0'], ret['z_std'] = rgb_map_0, disp_map_0, acc_map_0, z_std
     return ret
 
 
