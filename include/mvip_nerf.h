@@ -746,6 +746,29 @@ int mvip_scatter_raw(const float *raw_k, const int *idx, int64_t K, int64_t n, f
 int mvip_occupancy_lookup(const float *pts, int64_t P, const float *box, const int *cells, const int *words, void *out,
                           void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Regions: 3D-consistent inpainting masks (beyond the reference, which takes its masks as given;
+ * csrc/region.hip, mvip_nerf_amd/region.py).  A region is a set of cells of a box, stored exactly as an
+ * occupancy grid above (box = {bmin[3], inv[3]} and cells in HOST memory, words in DEVICE memory, the
+ * same cell, bit and tail conventions).  The one difference: inside(p) = in the box AND bit set.
+ *
+ * mvip_region_mark: pts [P,3]; every point in the box ORs its bit into words (in/out: bits already set
+ *   stay set).  Uses a vector atomic OR on the word: OR is commutative and idempotent, so the words do
+ *   not depend on the order of execution and the result is reproducible bit for bit.  P == 0: MVIP_OK,
+ *   nothing launched.
+ * mvip_region_accumulate: rows [B,11], z [B,S], weights [B,S] -> out [B] = sum over j of
+ *   (inside(rows[0:3] + rows[3:6] * z[b,j]) ? weights[b,j] : 0), the point in the expression of the
+ *   mvip_mlp_forward_rays* kernels.  A select: a NaN weight outside the region does not reach the sum.
+ *   Fixed summation order: one wave per ray, lane t adds j = t, t + 64, ... in ascending j, then one fixed
+ *   six-step DPP tree; a ray's result does not depend on B or on its neighbours.  S >= 1,
+ *   B*S <= 2^31 - 1.  B == 0: MVIP_OK, nothing launched.
+ * mvip_region_lookup: out [P] uint8 = inside(pts[p]), pts [P,3].  P == 0: MVIP_OK, nothing launched. */
+int mvip_region_mark(const float *pts, int64_t P, const float *box, const int *cells, int *words, void *stream);
+int mvip_region_accumulate(const float *rows, const float *z, const float *weights, int64_t B, int S, const float *box,
+                           const int *cells, const int *words, float *out, void *stream);
+int mvip_region_lookup(const float *pts, int64_t P, const float *box, const int *cells, const int *words, void *out,
+                       void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -173,6 +173,9 @@ _SIGNATURES = {
                                    _c_f, _c_f, _c_f]),
     'mvip_scatter_raw': (_int, [_c_f, _c_f, _i64, _i64, _c_f, _c_f]),
     'mvip_occupancy_lookup': (_int, [_c_f, _i64, ctypes.POINTER(_flt), ctypes.POINTER(_int), _c_f, _c_f, _c_f]),
+    'mvip_region_mark': (_int, [_c_f, _i64, ctypes.POINTER(_flt), ctypes.POINTER(_int), _c_f, _c_f]),
+    'mvip_region_accumulate': (_int, [_c_f, _c_f, _c_f, _i64, _int, ctypes.POINTER(_flt), ctypes.POINTER(_int), _c_f, _c_f, _c_f]),
+    'mvip_region_lookup': (_int, [_c_f, _i64, ctypes.POINTER(_flt), ctypes.POINTER(_int), _c_f, _c_f, _c_f]),
 }
 
 # every symbol include/mvip_nerf.h declares; tests check the built library exports all of them

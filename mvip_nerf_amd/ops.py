@@ -1900,3 +1900,41 @@ def occupancy_lookup(pts, box, cells, words):
     cbox, ccells = _occ_args(box, cells)
     call('mvip_occupancy_lookup', ptr(p), p.shape[0], cbox, ccells, ptr(words, _I32), ptr(out, torch.uint8), stream())
     return out
+
+
+# regions: 3D-consistent inpainting masks (beyond the reference, mvip_nerf_amd/region.py, csrc/region.hip) -----------------
+# The grid arguments are occupancy's; inside(p) = in the box AND bit set.
+
+def region_mark(pts, box, cells, words):
+    """OR the bit of every point of pts [P, 3] that lies in the box into `words` (in place; returns words)."""
+    p = _f32c(pts.reshape(-1, 3))
+    if tuple(words.shape) != (occupancy_words(cells),):
+        raise _lib.MvipError(f'region_mark: {tuple(words.shape)} words for cells {tuple(cells)}')
+    cbox, ccells = _occ_args(box, cells)
+    call('mvip_region_mark', ptr(p), p.shape[0], cbox, ccells, ptr(words, _I32), stream())
+    return words
+
+
+def region_accumulate(rows, z, weights, box, cells, words):
+    """out [B] = sum over j of (inside(rows[:, 0:3] + rows[:, 3:6] * z[:, j]) ? weights[:, j] : 0); rows [B, 11], z and
+    weights [B, S].  No autograd: the inputs are read as they are."""
+    rows, z, weights = _f32c(rows.detach()), _f32c(z.detach()), _f32c(weights.detach())
+    B, S = z.shape
+    if tuple(rows.shape) != (B, 11) or tuple(weights.shape) != (B, S) or tuple(words.shape) != (occupancy_words(cells),):
+        raise _lib.MvipError(f'region_accumulate: rows {tuple(rows.shape)}, z {tuple(z.shape)}, weights {tuple(weights.shape)}, '
+                             f'{tuple(words.shape)} words for cells {tuple(cells)}')
+    out = torch.empty(B, device=z.device, dtype=_F32)
+    cbox, ccells = _occ_args(box, cells)
+    call('mvip_region_accumulate', ptr(rows), ptr(z), ptr(weights), B, S, cbox, ccells, ptr(words, _I32), ptr(out), stream())
+    return out
+
+
+def region_lookup(pts, box, cells, words):
+    """inside(p) of pts [P, 3]: uint8 [P], 1 = in the box and in a cell of the region."""
+    p = _f32c(pts.reshape(-1, 3))
+    if tuple(words.shape) != (occupancy_words(cells),):
+        raise _lib.MvipError(f'region_lookup: {tuple(words.shape)} words for cells {tuple(cells)}')
+    out = torch.empty(p.shape[0], device=p.device, dtype=torch.uint8)
+    cbox, ccells = _occ_args(box, cells)
+    call('mvip_region_lookup', ptr(p), p.shape[0], cbox, ccells, ptr(words, _I32), ptr(out, torch.uint8), stream())
+    return out

@@ -169,7 +169,8 @@ FUSED_RENDER_MAX_RAYS = int(os.environ.get('MVIP_FUSED_RENDER_MAX_RAYS', '4096')
 
 def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False, lindisp=False, perturb=0.,
                 N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0., pytest=False,
-                sigma_loss=None, verbose=False, need_alpha=False, detach_weights=False, coarse_grad=True, occupancy=None):
+                sigma_loss=None, verbose=False, need_alpha=False, detach_weights=False, coarse_grad=True, occupancy=None,
+                region=None):
     """DS_NeRF/run.py:1703-1847: stratified depths -> coarse MLP -> compositing -> inverse-CDF
     resampling + merge -> fine MLP -> compositing.  Five kernel launches per chunk on the native
     path (z, MLP, composite, sample+merge, MLP, composite) instead of ~150 torch ops.
@@ -182,7 +183,12 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
 
     `occupancy` (extension, default None = every path as it is without it): an occupancy.OccupancyGrid; no-grad renders
     only.  The render is the one this chain would produce if the network's raw output were zero at every sample whose
-    point lies in a cell the grid marks empty, and the network is not evaluated there (_render_rays_occupancy)."""
+    point lies in a cell the grid marks empty, and the network is not evaluated there (_render_rays_occupancy).
+
+    `region` (extension, default None = no launch and no key added): a region.Region; the returned dict gains
+    'region_map' [B], per ray the sum of the FINAL pass's weights over the samples whose point lies inside the region
+    (one launch, Region.accumulate on this call's own `weights` / `z_vals`, whichever route produced them).  It carries no
+    gradient.  ValueError: not a Region, a region on another device than the rays, ray rows that are not 11 columns."""
     ray_batch = ray_batch.float() if ray_batch.dtype != torch.float32 else ray_batch
     ray_batch = ray_batch.contiguous()
     N_rays, ncols = ray_batch.shape
@@ -211,10 +217,15 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
     coarse_net = network_fn if network_fn is not None else (
         network_fine.alpha_model if getattr(network_fine, 'alpha_model', None) is not None else network_fine)
     fine_net = network_fn if network_fine is None else network_fine
+    if region is not None:
+        _check_region(region, rows, ncols)
     if occupancy is not None:
-        return _render_rays_occupancy(occupancy, rows, ncols, coarse_net, fine_net, network_query_fn, N_samples, retraw,
-                                      lindisp, perturb, N_importance, white_bkgd, raw_noise_std, pytest, sigma_loss,
-                                      need_alpha, detach_weights, t_rand)
+        ret = _render_rays_occupancy(occupancy, rows, ncols, coarse_net, fine_net, network_query_fn, N_samples, retraw,
+                                     lindisp, perturb, N_importance, white_bkgd, raw_noise_std, pytest, sigma_loss,
+                                     need_alpha, detach_weights, t_rand)
+        if region is not None:
+            ret['region_map'] = region.accumulate(rows, ret['z_vals'], ret['weights'])
+        return ret
     if (FUSED_RENDER and not torch.is_grad_enabled() and 0 < N_rays <= FUSED_RENDER_MAX_RAYS and N_samples == 64 and 0 < N_importance <= 64
             and ncols == 11 and sigma_loss is None and getattr(network_query_fn, '_mvip_native', False)
             and isinstance(coarse_net, NeRF) and isinstance(fine_net, NeRF)):
@@ -236,6 +247,8 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
             if need_alpha:
                 ret['alpha'], ret['alpha0'] = alpha, alpha0
             ret['rgb0'], ret['disp0'], ret['acc0'], ret['z_std'] = rgb0, disp0, acc0, z_std
+            if region is not None:
+                ret['region_map'] = region.accumulate(rows, z_vals, weights)
             return ret
     z_vals = ops.stratified_z(rows, N_samples, lindisp, t_rand)
 
@@ -272,11 +285,23 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
         ret['sigma_loss'] = sigma_loss.calculate_loss(rows[:, 0:3], rows[:, 3:6], rows[:, 8:11],
                                                       rows[:, 6:7], rows[:, 7:8], depths, network_query_fn,
                                                       network_fine)
+    if region is not None:
+        ret['region_map'] = region.accumulate(rows, z_vals, weights)
     if DEBUG:
         for k in ret:
             if torch.isnan(ret[k]).any() or torch.isinf(ret[k]).any():
                 print(f"! [Numerical Error] {k} contains nan or inf.")
     return ret
+
+
+def _check_region(region, rows, ncols):
+    from .region import Region
+    if not isinstance(region, Region):
+        raise ValueError(f'region must be a region.Region, got {type(region).__name__}')
+    if ncols != 11:
+        raise ValueError(f'region: ray rows of 11 columns (with view directions, no depth column) expected, got {ncols}')
+    if region.words.device != rows.device:
+        raise ValueError(f'region: the region is on {region.words.device}, the rays on {rows.device}; use region.to(device)')
 
 
 def _render_rays_occupancy(grid, rows, ncols, coarse_net, fine_net, network_query_fn, N_samples, retraw, lindisp, perturb,

@@ -1,0 +1,150 @@
+"""3D-consistent inpainting masks from a few annotated views (mvip_nerf_amd/region.py): lift the annotated views' masks
+into a region through the trained field's ray weights, render the region into every view, threshold.
+
+  python tools/propagate_masks.py --fixture [--views 0,15,29] [--views 0 ...] --out DIR
+  python tools/propagate_masks.py --checkpoint CKPT.tar --datadir SCENE [--factor 4] --views 0,15,29 --out DIR
+
+--fixture trains the scene-1 fixture (tests/golden/scene1_small.npz, the 1,500-iteration recipe of
+tools/render_occupancy_ab.py::train_scene1) and annotates with the fixture's own masks; --checkpoint / --datadir load a
+model in the reference's .tar format and a SPIn-NeRF style scene, and annotate with the scene's label/*.png of the views
+named.  --views may be repeated: one run per annotated set, the field trained or loaded once.
+
+Per set, into DIR/views_<set>/: label/NNNNNN.png (0 / 255, one per view, the layout load_llff._load_data reads; with
+--datadir the scene's own file names), region.npz (Region.save), with --carve-preview VIEW that view rendered with and
+without region.carve() as occupancy (carve_plain.png, carve_cut.png).  One JSON (printed, and DIR/mask_propagation.json):
+per-view IoU against the dataset's masks where they exist, the copy baseline (the nearest annotated view's mask copied
+unchanged), the region's cell count and share, seconds per stage.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+from mvip_nerf_amd import run                                                # noqa: E402
+from mvip_nerf_amd.region import Region, propagate_masks                     # noqa: E402
+from mvip_nerf_amd.run_nerf_helpers import to8b                              # noqa: E402
+
+
+def iou(a, b):
+    return float((a & b).sum()) / max(float((a | b).sum()), 1.0)
+
+
+def copy_baseline(masks, poses, annotated, valid):
+    """Per view that is not annotated and has a dataset mask: IoU of the nearest annotated view's mask (nearest by camera
+    position) copied unchanged."""
+    out = {}
+    for v in range(len(masks)):
+        if v not in annotated and valid[v]:
+            a = min(annotated, key=lambda k: np.linalg.norm(poses[k, :3, 3] - poses[v, :3, 3]))
+            out[v] = iou(masks[v], masks[a])
+    return out
+
+
+def fixture_scene(device, iters):
+    from tools import render_occupancy_ab as T
+    scene = T.train_scene1(device, iters)
+    masks = np.load(T.FIXTURE)['masks'].astype(bool)
+    names = ['{:06d}'.format(i) for i in range(len(masks))]
+    return scene['te'], (scene['H'], scene['W'], scene['focal']), scene['poses'], masks, np.ones(len(masks), bool), names, \
+        scene['near'], scene['far'], {'fixture': 'tests/golden/scene1_small.npz', 'iterations': iters, 'held_out_view': scene['held']}
+
+
+def checkpoint_scene(device, ckpt, datadir, factor):
+    from mvip_nerf_amd.load_llff import load_llff_data
+    from tools.extract_mesh import load_model
+    kw, step = load_model(ckpt, 'mlp', device)
+    images, poses, bds, _, _, masks, _, mask_indices = load_llff_data(datadir, factor=factor)
+    H, W, focal = (float(v) for v in poses[0, :3, -1])
+    root = os.path.join(datadir, 'images' if factor is None else f'images_{factor}', 'RGB_inpainted')
+    names = [f.split('.')[0] for f in sorted(os.listdir(root)) if f.endswith(('JPG', 'jpg', 'jpeg', 'png'))]
+    if not (len(names) == len(poses) == len(masks)):
+        raise SystemExit(f'{datadir}: {len(names)} images, {len(poses)} poses, {len(masks)} masks: one of each per view expected')
+    valid = np.zeros(len(masks), bool)
+    valid[list(mask_indices)] = True
+    near, far = float(bds.min() * .9), float(bds.max() * 1.)
+    te = dict(kw, near=near, far=far)
+    return te, (int(H), int(W), focal), torch.from_numpy(poses[:, :3, :4].copy()).to(device), masks == 1, valid, names, near, far, \
+        {'checkpoint': ckpt, 'step': step, 'datadir': datadir, 'factor': factor}
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    ap.add_argument('--fixture', action='store_true')
+    ap.add_argument('--iters', type=int, default=1500, help='training iterations of --fixture')
+    ap.add_argument('--checkpoint')
+    ap.add_argument('--datadir')
+    ap.add_argument('--factor', type=int, default=4)
+    ap.add_argument('--views', action='append', help='annotated views, comma separated (default 0,15,29); may be repeated')
+    ap.add_argument('--out', required=True)
+    ap.add_argument('--cells', type=int, default=64)
+    ap.add_argument('--dilate', type=int, default=1)
+    ap.add_argument('--min-weight', type=float, default=None)
+    ap.add_argument('--threshold', type=float, default=0.5)
+    ap.add_argument('--carve-preview', type=int, default=None, metavar='VIEW')
+    a = ap.parse_args(argv)
+    if a.fixture == bool(a.checkpoint) or bool(a.checkpoint) != bool(a.datadir):
+        ap.error('either --fixture, or --checkpoint with --datadir')
+    dev = torch.device('cuda', 0)
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return out, time.perf_counter() - t0
+
+    (te, hwf, poses, masks, valid, names, near, far, source), t_model = timed(
+        lambda: fixture_scene(dev, a.iters) if a.fixture else checkpoint_scene(dev, a.checkpoint, a.datadir, a.factor))
+    poses_np = poses.cpu().numpy()
+    out = {'source': source, 'frame': [hwf[0], hwf[1]], 'views': len(masks), 'mask_share_of_frame': float(masks[valid].mean()),
+           'settings': {'cells': a.cells, 'dilate': a.dilate, 'min_weight': a.min_weight or 'default 1 / S', 'threshold': a.threshold},
+           'seconds_model': t_model, 'sets': []}
+    os.makedirs(a.out, exist_ok=True)
+    for spec in (a.views or ['0,15,29']):
+        annotated = [int(v) for v in spec.split(',')]
+        missing = [v for v in annotated if not valid[v]]
+        if missing:
+            raise SystemExit(f'views {missing} have no mask to annotate with')
+        folder = os.path.join(a.out, 'views_' + '_'.join(str(v) for v in annotated))
+        os.makedirs(os.path.join(folder, 'label'), exist_ok=True)
+        region, t_lift = timed(lambda: Region.from_masks(te, hwf, poses[annotated], torch.from_numpy(masks[annotated]).to(dev),
+                                                         near, far, cells=a.cells, min_weight=a.min_weight, dilate=a.dilate))
+        (soft, hard), t_prop = timed(lambda: propagate_masks(te, hwf, poses, region, near, far, a.threshold))
+        hard = hard.cpu().numpy()
+        region.save(os.path.join(folder, 'region.npz'))
+        for v, name in enumerate(names):
+            run._write_png(os.path.join(folder, 'label', name + '.png'), np.repeat(hard[v][..., None].astype(np.uint8) * 255, 3, -1))
+        ious = {v: iou(hard[v], masks[v]) for v in range(len(masks)) if valid[v]}
+        others = [v for v in ious if v not in annotated]
+        base = copy_baseline(masks, poses_np, annotated, valid)
+        rec = {'annotated': annotated, 'region_cells': region.count(), 'region_share_of_box': region.fraction(),
+               'box_min': [float(v) for v in region.bmin], 'box_max': [float(v) for v in region.bmax],
+               'iou_per_view': {str(v): ious[v] for v in ious}, 'copy_baseline_per_view': {str(v): base[v] for v in base},
+               'mean_iou_other_views': float(np.mean([ious[v] for v in others])), 'min_iou_other_views': float(np.min([ious[v] for v in others])),
+               'copy_baseline_mean': float(np.mean(list(base.values()))), 'copy_baseline_min': float(np.min(list(base.values()))),
+               'mean_iou_annotated_views': float(np.mean([ious[v] for v in annotated])),
+               'seconds_lift': t_lift, 'seconds_propagate_all_views': t_prop}
+        if a.carve_preview is not None:
+            with torch.no_grad():
+                kw = dict(te, near=near, far=far)
+                plain = run.render(hwf[0], hwf[1], hwf[2], chunk=1 << 15, c2w=poses[a.carve_preview], **kw)[0]
+                cut = run.render(hwf[0], hwf[1], hwf[2], chunk=1 << 15, c2w=poses[a.carve_preview], occupancy=region.carve(), **kw)[0]
+            run._write_png(os.path.join(folder, 'carve_plain.png'), to8b(np.nan_to_num(plain.cpu().numpy())))
+            run._write_png(os.path.join(folder, 'carve_cut.png'), to8b(np.nan_to_num(cut.cpu().numpy())))
+            rec['carve_preview'] = {'view': a.carve_preview, 'pixels_changed': float(((plain - cut).abs().amax(-1) > 1 / 255).float().mean())}
+        out['sets'].append(rec)
+    print(json.dumps(out, indent=1))
+    json.dump(out, open(os.path.join(a.out, 'mask_propagation.json'), 'w'), indent=1)
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())
