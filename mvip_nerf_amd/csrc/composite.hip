@@ -42,17 +42,19 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(
     const float a = sums[0], d = sums[1];
     float gc[3] = {0.f, 0.f, 0.f};
     if (g_rgb) { gc[0] = g_rgb[ray * 3]; gc[1] = g_rgb[ray * 3 + 1]; gc[2] = g_rgb[ray * 3 + 2]; }
-    // disp = 1 / max(1e-10, depth/acc)
-    float gq = 0.f;
+    // disp = 1 / max(1e-10, q), q = depth/acc.  Its cotangent reaches the weight of sample s as (gq / acc) (z_s - q): formed
+    // from the difference z_s - q, not as gq/acc * z_s - gq*depth/acc^2 -- two separately rounded terms that cancel (to zero
+    // on a ray with a single non-zero weight) and leave a rounding error of the large terms, amplified by 1/acc.
+    float q = 0.f, gqa = 0.f;
     if (g_disp) {
-        const float q = d / a;
+        q = d / a;
         const float m = (q != q) ? q : fmaxf(1e-10f, q);
         const float gm = -g_disp[ray] / (m * m);
-        gq = (1e-10f > q) ? 0.f : (q == 1e-10f ? .5f * gm : gm);
+        const float gq = (1e-10f > q) ? 0.f : (q == 1e-10f ? .5f * gm : gm);
+        gqa = gq / a;
     }
-    float gd = (g_depth ? g_depth[ray] : 0.f);
+    const float gd = (g_depth ? g_depth[ray] : 0.f);
     float ga = (g_acc ? g_acc[ray] : 0.f);
-    if (g_disp) { gd += gq / a; ga -= gq * d / (a * a); }
     if (flags & MVIP_COMP_WHITE) ga -= (gc[0] + gc[1]) + gc[2];
     const bool detach = flags & MVIP_COMP_DETACHW;
 
@@ -61,6 +63,7 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(
     for (int i = 0; i < ITEMS; ++i) {
         const int s = l * ITEMS + i;
         float g = gd * st.z[i] + ga;
+        if (g_disp) g += gqa * (st.z[i] - q);
         if (g_w && st.valid[i]) g += g_w[ray * S + s];
         if (!detach) g += (gc[0] * st.c[i][0] + gc[1] * st.c[i][1]) + gc[2] * st.c[i][2];
         Gw[i] = st.valid[i] ? g : 0.f;

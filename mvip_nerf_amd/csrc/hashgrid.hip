@@ -29,11 +29,14 @@ struct HgLevel {           // one row of the level table (device memory, indexed
 };
 
 __device__ __forceinline__ uint32_t hg_index(uint32_t cx, uint32_t cy, uint32_t cz, uint32_t res, uint32_t size) {
-    uint32_t stride = 1, index = 0;
+    // 64-bit stride: resolution^2 reaches 2^32 at resolution 65536, where a 32-bit stride wraps to 0 and a hashed level
+    // would be indexed as a dense one (stride <= size < 2^32 before each product, so 64 bits hold it)
+    uint64_t stride = 1;
+    uint32_t index = 0;
     const uint32_t c[3] = {cx, cy, cz};
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
-        if (stride <= size) { index += c[d] * stride; stride *= res; }
+        if (stride <= size) { index += c[d] * (uint32_t)stride; stride *= res; }
     }
     if (size < stride) index = cx ^ (cy * 2654435761u) ^ (cz * 805459861u);
     return index % size;

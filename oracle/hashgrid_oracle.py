@@ -1,4 +1,4 @@
-"""TEST INFRASTRUCTURE ONLY -- CPU restatement (torch, fp32) of the reference's NeRF_TCNN forward
+"""TEST INFRASTRUCTURE ONLY -- CPU restatement (torch; fp32 on fp32 inputs, fp64 on fp64 inputs) of the reference's NeRF_TCNN forward
 (DS_NeRF/run_nerf_helpers_tcnn.py:88-112).  The encodings and MLPs are tiny-cuda-nn's (third-party, NVIDIA-only,
 absent from the reference tree, unpinned in requirements_df.txt): restated from the published algorithm
 (Mueller et al. 2022; tiny-cuda-nn include/tiny-cuda-nn/encodings/grid.h and spherical_harmonics.h).
@@ -11,9 +11,13 @@ PRIMES = (1, 2654435761, 805459861)
 M32 = 0xFFFFFFFF
 
 
-def grid_encode(x01, table, levels):
-    """x01 [P,3] in [0,1]; table [n_entries, 2]; levels [16,4] int32 words -> [P, 32] (level-major, feature-minor)."""
+def grid_encode(x01, table, levels, unit_weights=False):
+    """x01 [P,3] in [0,1]; table [n_entries, 2]; levels [16,4] int32 words -> [P, 32] (level-major, feature-minor).
+    Positions and weights are formed in x01's dtype, the sums in the wider of x01's and the table's (float32 inputs:
+    float32 throughout; float64 inputs: an fp64 reference).  unit_weights=True replaces every corner weight by 1, so that
+    the gradient w.r.t. the table COUNTS the contributions to each entry."""
     P = x01.shape[0]
+    dt = torch.promote_types(x01.dtype, table.dtype)
     out = []
     lv = levels.astype(np.int64) & M32
     for scale_bits, res, off, size in lv:
@@ -22,13 +26,14 @@ def grid_encode(x01, table, levels):
         fl = torch.floor(pos)
         w = pos - fl
         cell = fl.to(torch.int64) & M32
-        acc = torch.zeros(P, 2, dtype=torch.float32)
+        acc = torch.zeros(P, 2, dtype=dt)
         for k in range(8):
             bits = [(k >> d) & 1 for d in range(3)]
             c = [(cell[:, d] + bits[d]) & M32 for d in range(3)]
-            wk = torch.ones(P, dtype=torch.float32)
+            wk = torch.ones(P, dtype=dt)
             for d in range(3):
-                wk = wk * (w[:, d] if bits[d] else 1.0 - w[:, d])
+                if not unit_weights:
+                    wk = wk * (w[:, d] if bits[d] else 1.0 - w[:, d])
             stride, index = 1, torch.zeros(P, dtype=torch.int64)
             for d in range(3):
                 if stride <= size:

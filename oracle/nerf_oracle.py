@@ -230,11 +230,12 @@ def render_rays(ray_batch, p_coarse, p_fine, N_samples, N_importance=0, lindisp=
 # ----------------------------------------------------------------------------------------------
 
 def depth2xyz(depth, K):
-    """depth [H,W], K 3x3 -> [H,W,3] camera-space points (x right, y down, z = depth)."""
+    """depth [H,W], K 3x3 -> [H,W,3] camera-space points (x right, y down, z = depth), in depth's dtype
+    (a float64 depth with a float64 K evaluates every operation in fp64)."""
     H, W = depth.shape
     fx, fy, cx, cy = K[0, 0], K[1, 1], K[0, 2], K[1, 2]
-    hh = torch.arange(H, dtype=torch.float32)[:, None].expand(H, W)
-    ww = torch.arange(W, dtype=torch.float32)[None, :].expand(H, W)
+    hh = torch.arange(H, dtype=depth.dtype)[:, None].expand(H, W)
+    ww = torch.arange(W, dtype=depth.dtype)[None, :].expand(H, W)
     x = (ww - cx) * depth / fx
     y = (hh - cy) * depth / fy
     return torch.stack([x, y, depth], -1)
@@ -251,13 +252,17 @@ def normal_fit_unfold(points, k=31):
     return n.squeeze(-1).permute(0, 3, 1, 2)
 
 
-def normal_fit_boxsum(points, k=31):
+def normal_fit_boxsum(points, k=31, keep_double=False, round_sums=False):
     """Same quantity through nine zero-padded box sums + a closed-form symmetric 3x3 solve
-    (the formulation the HIP kernel uses).  fp64 accumulation for use as a checker."""
+    (the formulation the HIP kernel uses).  fp64 accumulation for use as a checker; keep_double=True
+    returns the float64 result itself (autograd then runs in fp64 to the end); round_sums=True rounds the
+    nine box sums to fp32 on the way (the kernel's storage format: how far that alone moves the result)."""
     P = points.double()
     x, y, z = P[:, 0:1], P[:, 1:2], P[:, 2:3]
     mom = torch.cat([x * x, x * y, x * z, y * y, y * z, z * z, x, y, z], 1)
     box = F.avg_pool2d(mom, k, stride=1, padding=(k - 1) // 2, count_include_pad=True) * (k * k)
+    if round_sums:
+        box = box.float().double()
     sxx, sxy, sxz, syy, syz, szz, sx, sy, sz = [box[:, i] for i in range(9)]
     c00 = syy * szz - syz * syz
     c01 = sxz * syz - sxy * szz
@@ -269,7 +274,8 @@ def normal_fit_boxsum(points, k=31):
     nx = (c00 * sx + c01 * sy + c02 * sz) / det
     ny = (c01 * sx + c11 * sy + c12 * sz) / det
     nz = (c02 * sx + c12 * sy + c22 * sz) / det
-    return torch.stack([nx, ny, nz], 1).float()
+    n = torch.stack([nx, ny, nz], 1)
+    return n if keep_double else n.float()
 
 # ----------------------------------------------------------------------------------------------
 # misc                                                  DS_NeRF/run_nerf_helpers.py:15-18
