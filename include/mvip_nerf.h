@@ -769,6 +769,21 @@ int mvip_region_accumulate(const float *rows, const float *z, const float *weigh
 int mvip_region_lookup(const float *pts, int64_t P, const float *box, const int *cells, const int *words, void *out,
                        void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Ray distortion loss (mip-NeRF 360, eq. 15; beyond the reference, which has no regulariser of this kind and
+ * no call site this replaces; csrc/distortion.hip).  rows [B,ncols] (ncols 8 or 11; near = column 6,
+ * far = column 7), z [B,S] in ascending order along the ray, weights [B,S].
+ *   s_j = (z_j - near) / (far - near), with lindisp != 0 (1/z_j - 1/near) / (1/far - 1/near), in fp32;
+ *   sample j < S-1 owns [s_j, s_{j+1}] (midpoint m_j, width d_j), the last sample the point s_{S-1} (d = 0);
+ *   loss[b] = sum_i sum_j w_i w_j |m_i - m_j| + (1/3) sum_j w_j^2 d_j
+ *   grad[b,k] = d loss[b] / d w_k = 2 sum_j w_j |m_k - m_j| + (2/3) w_k d_k      (optional: NULL = loss only)
+ * One launch, one wave per ray, sums of non-negative terms in a fixed order; a ray's result does not depend
+ * on B or on its neighbours, and the loss does not depend on whether grad is asked for.  A non-finite
+ * weight or depth (or far == near) makes that ray's loss and gradient row non-finite and touches no other.
+ * S >= 1, B*S <= 2^31 - 1.  B == 0: MVIP_OK, nothing launched. */
+int mvip_distortion_loss(const float *rows, int ncols, const float *z, const float *weights, int64_t B, int S, int lindisp,
+                         float *loss, float *grad, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

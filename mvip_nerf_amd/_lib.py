@@ -176,6 +176,7 @@ _SIGNATURES = {
     'mvip_region_mark': (_int, [_c_f, _i64, ctypes.POINTER(_flt), ctypes.POINTER(_int), _c_f, _c_f]),
     'mvip_region_accumulate': (_int, [_c_f, _c_f, _c_f, _i64, _int, ctypes.POINTER(_flt), ctypes.POINTER(_int), _c_f, _c_f, _c_f]),
     'mvip_region_lookup': (_int, [_c_f, _i64, ctypes.POINTER(_flt), ctypes.POINTER(_int), _c_f, _c_f, _c_f]),
+    'mvip_distortion_loss': (_int, [_c_f, _int, _c_f, _c_f, _i64, _int, _int, _c_f, _c_f, _c_f]),
 }
 
 # every symbol include/mvip_nerf.h declares; tests check the built library exports all of them

@@ -1938,3 +1938,38 @@ def region_lookup(pts, box, cells, words):
     cbox, ccells = _occ_args(box, cells)
     call('mvip_region_lookup', ptr(p), p.shape[0], cbox, ccells, ptr(words, _I32), ptr(out, torch.uint8), stream())
     return out
+
+
+# ray distortion loss (mip-NeRF 360 eq. 15; beyond the reference, csrc/distortion.hip) ------------------------------------------
+
+class _DistortionLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, weights, z, rows, lindisp):
+        B, S = z.shape
+        loss = torch.empty((B,), device=z.device, dtype=_F32)
+        grad = torch.empty((B, S), device=z.device, dtype=_F32) if ctx.needs_input_grad[0] else None
+        call('mvip_distortion_loss', ptr(rows), rows.shape[1], ptr(z), ptr(weights), B, S, int(bool(lindisp)), ptr(loss),
+             ptr(grad), stream())
+        ctx.save_for_backward(grad)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        grad, = ctx.saved_tensors
+        return g_loss[:, None] * grad, None, None, None
+
+
+def distortion_loss(weights, z, rows, lindisp=False):
+    """loss [B] = sum_i sum_j w_i w_j |m_i - m_j| + (1/3) sum_j w_j^2 d_j over the normalised intervals of z [B, S] (ascending
+    along the ray; near / far from rows[:, 6:8], rows [B, 8] or [B, 11]; the conventions are csrc/distortion.hip's).  One
+    launch; when `weights` requires grad the same launch writes d loss / d weights, and the backward is one elementwise
+    product.  Gradient goes to `weights` only (the fine depths are detached resamples)."""
+    if not (torch.is_tensor(weights) and torch.is_tensor(z) and torch.is_tensor(rows)) or z.dim() != 2 \
+            or tuple(weights.shape) != tuple(z.shape) or rows.dim() != 2 or rows.shape[0] != z.shape[0] \
+            or rows.shape[1] not in (8, 11) or z.shape[1] < 1:
+        shape = lambda t: tuple(t.shape) if torch.is_tensor(t) else type(t).__name__
+        raise _lib.MvipError(f'distortion_loss: weights {shape(weights)}, z {shape(z)}, rows {shape(rows)}')
+    if not (weights.is_cuda and z.device == weights.device and rows.device == weights.device):
+        raise _lib.MvipError(f'distortion_loss: weights on {weights.device}, z on {z.device}, rows on {rows.device}; the HIP '
+                             'path has no CPU fallback')
+    return _DistortionLoss.apply(_f32c(weights), _f32c(z.detach()), _f32c(rows.detach()), bool(lindisp))

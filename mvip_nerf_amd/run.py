@@ -170,7 +170,7 @@ FUSED_RENDER_MAX_RAYS = int(os.environ.get('MVIP_FUSED_RENDER_MAX_RAYS', '4096')
 def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False, lindisp=False, perturb=0.,
                 N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0., pytest=False,
                 sigma_loss=None, verbose=False, need_alpha=False, detach_weights=False, coarse_grad=True, occupancy=None,
-                region=None):
+                region=None, distortion=False):
     """DS_NeRF/run.py:1703-1847: stratified depths -> coarse MLP -> compositing -> inverse-CDF
     resampling + merge -> fine MLP -> compositing.  Five kernel launches per chunk on the native
     path (z, MLP, composite, sample+merge, MLP, composite) instead of ~150 torch ops.
@@ -188,7 +188,14 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
     `region` (extension, default None = no launch and no key added): a region.Region; the returned dict gains
     'region_map' [B], per ray the sum of the FINAL pass's weights over the samples whose point lies inside the region
     (one launch, Region.accumulate on this call's own `weights` / `z_vals`, whichever route produced them).  It carries no
-    gradient.  ValueError: not a Region, a region on another device than the rays, ray rows that are not 11 columns."""
+    gradient.  ValueError: not a Region, a region on another device than the rays, ray rows that are not 11 columns.
+
+    `distortion` (extension, default False = no launch and no key added): with True the returned dict gains 'dist_loss' [B],
+    ops.distortion_loss (mip-NeRF 360 eq. 15) of the FINAL pass's `weights` / `z_vals`, and with N_importance > 0
+    'dist_loss0' [B], the same of the coarse pass's (as rgb0 mirrors rgb_map); both with this call's `lindisp`, each carrying
+    whatever gradient its weights carry (dist_loss0 none under coarse_grad=False).  The two-launch route does not expose the
+    coarse weights, so the call takes the six-launch chain (bit-identical).  ValueError together with `occupancy`: it is a
+    training loss, like sigma_loss."""
     ray_batch = ray_batch.float() if ray_batch.dtype != torch.float32 else ray_batch
     ray_batch = ray_batch.contiguous()
     N_rays, ncols = ray_batch.shape
@@ -219,6 +226,8 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
     fine_net = network_fn if network_fine is None else network_fine
     if region is not None:
         _check_region(region, rows, ncols)
+    if distortion and occupancy is not None:
+        raise ValueError('distortion: the distortion loss is a training loss; occupancy skipping is for no-grad renders only')
     if occupancy is not None:
         ret = _render_rays_occupancy(occupancy, rows, ncols, coarse_net, fine_net, network_query_fn, N_samples, retraw,
                                      lindisp, perturb, N_importance, white_bkgd, raw_noise_std, pytest, sigma_loss,
@@ -226,7 +235,7 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
         if region is not None:
             ret['region_map'] = region.accumulate(rows, ret['z_vals'], ret['weights'])
         return ret
-    if (FUSED_RENDER and not torch.is_grad_enabled() and 0 < N_rays <= FUSED_RENDER_MAX_RAYS and N_samples == 64 and 0 < N_importance <= 64
+    if (FUSED_RENDER and not distortion and not torch.is_grad_enabled() and 0 < N_rays <= FUSED_RENDER_MAX_RAYS and N_samples == 64 and 0 < N_importance <= 64
             and ncols == 11 and sigma_loss is None and getattr(network_query_fn, '_mvip_native', False)
             and isinstance(coarse_net, NeRF) and isinstance(fine_net, NeRF)):
         c16, f16 = coarse_net._infer16(), fine_net._infer16()
@@ -260,6 +269,7 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
 
     if N_importance > 0:
         rgb_map_0, disp_map_0, acc_map_0, alpha0 = rgb_map, disp_map, acc_map, alpha
+        weights_0, z_vals_0 = weights, z_vals
         u = _uniforms((N_rays,), N_importance, perturb == 0., pytest, dev)
         z_samples, z_vals, z_std, _, _ = ops.sample_pdf_merge(z_vals, weights, u)
         run_fn = network_fn if network_fine is None else network_fine
@@ -287,6 +297,11 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
                                                       network_fine)
     if region is not None:
         ret['region_map'] = region.accumulate(rows, z_vals, weights)
+    if distortion:
+        bounds = rows if rows.shape[1] in (8, 11) else rows[:, :8].contiguous()      # near / far are columns 6, 7 either way
+        ret['dist_loss'] = ops.distortion_loss(weights, z_vals, bounds, lindisp)
+        if N_importance > 0:
+            ret['dist_loss0'] = ops.distortion_loss(weights_0, z_vals_0, bounds, lindisp)
     if DEBUG:
         for k in ret:
             if torch.isnan(ret[k]).any() or torch.isinf(ret[k]).any():

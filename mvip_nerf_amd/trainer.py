@@ -87,6 +87,7 @@ class SecondStageTrainer:
         self.guidance = guidance                       # Pretrain_Model-like object with cal_loss(), or None
         self.rng = np.random.RandomState(1234)         # same draw on every rank (view choice must agree)
         self.N_rand = args.N_rand
+        self.last_distortion = None                    # the step's distortion term (detached scalar), None when off
         # one flat bucket, reduced as two asynchronous halves [coarse network | fine network] (dist_utils.OverlappedGradBuckets);
         # MVIP_OVERLAP_ALLREDUCE=0 restores the single blocking all_reduce after the backward (A/B switch, same values)
         n_coarse = len(list(self.kw_train['network_fn'].parameters())) if self.kw_train.get('network_fn') is not None else 0
@@ -243,7 +244,10 @@ class SecondStageTrainer:
                 loss_sds = args.sds_loss_weight * self.guidance.cal_loss(i, rgbs4, normal_map, None, combin_rgb, None,
                                                                          mask, mask4, 1)
 
-        # 3. supervision batches: unmasked colour rays and inpainted-depth rays
+        # 3. supervision batches: unmasked colour rays and inpainted-depth rays; with distortion_lambda > 0 (extension, default
+        # off: no keyword passed, the step as it is) these two renders also return the ray distortion loss
+        dist_lambda = float(getattr(args, 'distortion_lambda', 0.) or 0.)
+        kw_sup = dict(self.kw_train, distortion=True) if dist_lambda > 0 else self.kw_train
         if getattr(sc, 'sets', None) is not None or records is not None:
             rays_c, target_clf, _ = sc.next_batch('rays_rgb_clf', self.N_rand, None if records is None else records[0])
             rays_d, _, target_inp = sc.next_batch('rays_inp', self.N_rand, None if records is None else records[1])
@@ -254,8 +258,8 @@ class SecondStageTrainer:
                 dim, torch.arange(min(self.rank, t.shape[dim]), t.shape[dim], self.world, device=t.device))
             rays_c, target_clf = take(rays_c, 1), take(target_clf, 0)
             rays_d, target_inp = take(rays_d, 1), take(target_inp, 0)
-            r2 = self._render_records(rays_c, retraw=True, **self.kw_train)
-            r3 = self._render_records(rays_d, retraw=True, **self.kw_train)
+            r2 = self._render_records(rays_c, retraw=True, **kw_sup)
+            r3 = self._render_records(rays_d, retraw=True, **kw_sup)
             n_clf_local, n_inp_local = rays_c.shape[1], rays_d.shape[1]
         else:
             g = torch.Generator(device=self.device).manual_seed(10007 * (i + 1))
@@ -263,12 +267,12 @@ class SecondStageTrainer:
                                                   generator=g)]
             n_clf = n_inp = self.N_rand
             pick = self._shard(pick)
-            r2 = self._render_pixels(pose, pick, retraw=True, **self.kw_train)
+            r2 = self._render_pixels(pose, pick, retraw=True, **kw_sup)
             target_clf = sc.images[img_i].reshape(-1, 3)[pick]
             pick_d = sc.masked_idx[torch.randint(0, sc.masked_idx.numel(), (self.N_rand,), device=self.device,
                                                  generator=g)]
             pick_d = self._shard(pick_d)
-            r3 = self._render_pixels(pose, pick_d, retraw=True, **self.kw_train)
+            r3 = self._render_pixels(pose, pick_d, retraw=True, **kw_sup)
             target_inp = sc.depths[img_i].reshape(-1)[pick_d]
             n_clf_local, n_inp_local = pick.numel(), pick_d.numel()
         rays_rendered += n_clf_local + n_inp_local
@@ -288,6 +292,18 @@ class SecondStageTrainer:
             # iteration to have the reference's cost structure: a plain colour loss stands in
             wm = sel.numel() / max(masked_idx.numel(), 1)
             loss = loss + args.sds_loss_weight * img2mse(rgb_masked, sc.images[img_i].reshape(-1, 3)[sel]) * wm
+        # ray distortion loss of the two supervision renders (mip-NeRF 360 eq. 15; the masked SDS render and the neighbour views
+        # are not regularised), shard means weighted like the terms above, empty shards skipped
+        self.last_distortion = None
+        if dist_lambda > 0:
+            dist = 0.
+            for r, n_local, wgt in ((r2, n_clf_local, wc), (r3, n_inp_local, wi)):
+                if n_local:
+                    per_ray = r['dist_loss'] + r['dist_loss0'] if 'dist_loss0' in r else r['dist_loss']
+                    dist = dist + per_ray.mean() * wgt
+            if torch.is_tensor(dist):
+                self.last_distortion = (dist_lambda * dist).detach()
+                loss = loss + dist_lambda * dist
         if isinstance(self.bucket, OverlappedGradBuckets):
             self.bucket.begin(self.dist, self.world)       # the coarse half is reduced while the masked render's backward runs
         try:
