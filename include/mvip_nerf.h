@@ -139,6 +139,9 @@ int mvip_mlp_forward_rays16(const float *packed16, const float *rows, const floa
                             float *raw, void *stream);
 int mvip_mlp_forward_points16(const float *packed16, const float *pts, const float *dirs, int64_t P,
                               float *raw, void *stream);
+/* Test probe of the 16-point kernels' input encoding: pts, dirs [P,3] -> out_old, out_new [P,96] (64 position channels,
+ * then 32 direction channels, zero padded), by the per-channel reference route and by the once-per-wave route the kernels run. */
+int mvip_mlp_encode16_probe(const float *pts, const float *dirs, int64_t P, float *out_old, float *out_new, void *stream);
 
 /* Folded inference image (ops.mlp_pack16 / NeRF.packed_w16, NeRF.fold_feature_inference): feature_linear has no
  * activation, so a no-grad forward evaluates the view layer as relu(W' h + Wv[:, 256:] e_dir + b') with

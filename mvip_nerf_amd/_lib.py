@@ -43,6 +43,7 @@ _SIGNATURES = {
     'mvip_mlp_forward_rays16': (_int, [_c_f, _c_f, _c_f, _i64, _int, _c_f, _c_f]),
     'mvip_mlp_forward_rays_stash16': (_int, [_c_f, _c_f, _c_f, _i64, _int, _c_f, _c_f, _c_f]),
     'mvip_mlp_forward_points16': (_int, [_c_f, _c_f, _c_f, _i64, _c_f, _c_f]),
+    'mvip_mlp_encode16_probe': (_int, [_c_f, _c_f, _i64, _c_f, _c_f, _c_f]),
     'mvip_render_coarse_fused': (_int, [_c_f, _c_f, _i64, _c_f, _int, _c_f, _c_f, _c_f, _int, _int, _int, _c_f, _c_f, _c_f, _c_f,
                                         _c_f, _c_f, _c_f, _c_f, _c_f]),
     'mvip_render_fine_fused': (_int, [_c_f, _c_f, _c_f, _i64, _c_f, _int, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f]),

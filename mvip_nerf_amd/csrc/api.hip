@@ -13,7 +13,8 @@ extern "C" int mvip_abi_version(void) { return MVIP_ABI_VERSION; }
 // results are WRONG).  The Python loader refuses such a library unless explicitly allowed.
 extern "C" int mvip_build_is_experiment(void) {
 #if defined(MVIP_EXPERIMENT_NO_FUSE_TAIL) || defined(MVIP_EXPERIMENT_CONV) || defined(MVIP_EXPERIMENT_GEMM) || \
-    defined(MVIP_EXPERIMENT_NO_BARRIER) || defined(MVIP_EXPERIMENT_NO_EPILOGUE) || defined(MVIP_EXPERIMENT_HG_ONE_ATOMIC)
+    defined(MVIP_EXPERIMENT_NO_BARRIER) || defined(MVIP_EXPERIMENT_NO_EPILOGUE) || defined(MVIP_EXPERIMENT_HG_ONE_ATOMIC) || \
+    defined(MVIP_EXPERIMENT_NO_ENCODING16)
     return 1;
 #else
     return 0;

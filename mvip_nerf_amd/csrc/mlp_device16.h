@@ -18,7 +18,8 @@ __device__ __forceinline__ void static_for(F &&f) {
     if constexpr (I < N) { f(ic<I>{}); static_for<N, F, I + 1>(static_cast<F &&>(f)); }
 }
 
-// channel c of the sinusoidal encoding of (x, y, z) with C real channels (Embedder.embed order)
+// channel c of the sinusoidal encoding of (x, y, z) with C real channels (Embedder.embed order).  The per-channel route: the
+// kernels use encode16_wave below, this one is kept as the reference of the test probe (mlp_encode16_probe.hip).
 template <int C>
 __device__ __forceinline__ float enc_channel(float x, float y, float z, int c) {
     const int m = c >= 3 ? c - 3 : 0;
@@ -53,6 +54,64 @@ template <int OFF>
 __device__ __forceinline__ void glds(const float *src_lane, float *dst_wave) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src_lane,
                                      (__attribute__((address_space(3))) void *)dst_wave, 16, OFF, 0);
+}
+
+// The encodings of a wave's 16 points, each sine / cosine pair evaluated ONCE per wave.  With enc_channel every lane fills its
+// own fragment channels: 48 calls, each a range reduction and both polynomials behind divergent branches, while the four
+// lane groups of a point all reduce the same 42 (octave, axis) arguments again.  Here lane (n, g) takes the arguments
+// j = g (mod 4) of point n -- 8 of the position's 30 (groups 2 and 3: 7) and 3 of the direction's 12 -- calls sincosf once for
+// each (the same values as sinf / cosf: rays.hip relies on it, tests/test_encode16.py checks it bit for bit) and writes both
+// results to a wave-private [point][channel] tile in LDS; the identity channels and the zero padding go there as well.  The
+// fragments are read back as 16-byte quads: emb[t] = channels 16 t + 4 g .. + 3, edir[t] likewise.
+// `stage` = 1024 floats (4 KB) owned by this wave alone.  The direction tile reuses the position tile's space in a second
+// pass.  LDS operations of one wave execute in issue order, so no barrier is needed, only that the compiler keeps the
+// order (wave_barrier); the caller must not let anything else write `stage` before its next workgroup barrier.
+// Quad q of point n is stored at quad q ^ n (direction: q ^ (n >> 1), 8 quads per point): the 16 lanes of a group read 16
+// different bank quads instead of one.
+constexpr int ENC_STAGE_FLOATS = 1024;
+__device__ __forceinline__ void encode16_wave(float *stage, int lane, float px, float py, float pz, float vx, float vy,
+                                              float vz, f32x4 (&emb)[4], f32x4 (&edir)[2]) {
+    const int n = lane & 15, g = lane >> 4;
+    // ---- position: [16][64], channels 0..2 identity, 3 + 6 oct + {axis: sin, 3 + axis: cos}, 63 zero
+    float *row = stage + n * 64;
+    auto at_p = [&](int c) -> float & { return row[(((c >> 2) ^ n) << 2) + (c & 3)]; };
+    at_p(g < 3 ? g : 63) = g == 0 ? px : (g == 1 ? py : (g == 2 ? pz : 0.f));
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int j = g + 4 * k;
+        const int oct = j / 3, axis = j - 3 * oct;
+        const float xv = axis == 0 ? px : (axis == 1 ? py : pz);
+        float s, c;
+        sincosf(xv * __int_as_float((127 + oct) << 23), &s, &c);
+        if (k < 7 || g < 2) {
+            at_p(3 + 6 * oct + axis) = s;
+            at_p(6 + 6 * oct + axis) = c;
+        }
+    }
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int t = 0; t < 4; ++t) emb[t] = ld4(row + (((4 * t + g) ^ n) << 2));
+    __builtin_amdgcn_wave_barrier();
+    // ---- direction: [16][32], channels 0..2 identity, 3..26 as above, 27..31 zero
+    row = stage + n * 32;
+    const int nd = n >> 1;
+    auto at_d = [&](int c) -> float & { return row[(((c >> 2) ^ nd) << 2) + (c & 3)]; };
+    at_d(g < 3 ? g : 27) = g == 0 ? vx : (g == 1 ? vy : (g == 2 ? vz : 0.f));
+    at_d(28 + g) = 0.f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int j = g + 4 * k;
+        const int oct = j / 3, axis = j - 3 * oct;
+        const float xv = axis == 0 ? vx : (axis == 1 ? vy : vz);
+        float s, c;
+        sincosf(xv * __int_as_float((127 + oct) << 23), &s, &c);
+        at_d(3 + 6 * oct + axis) = s;
+        at_d(6 + 6 * oct + axis) = c;
+    }
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int t = 0; t < 2; ++t) edir[t] = ld4(row + (((4 * t + g) ^ nd) << 2));
+    __builtin_amdgcn_wave_barrier();
 }
 
 // NSLOT = ring slots of 16 KB.  WRAP (the persistent kernel, mlp_fwd16.hip): chunk indices past the end of the image wrap to

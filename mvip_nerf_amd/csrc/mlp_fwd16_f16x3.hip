@@ -313,24 +313,35 @@ mlp_forward_f16x3_w16_kernel(const float *__restrict__ img, const float *__restr
             }
         }
     };
-    // encoded point: 64 units (63 + a zero) = two k-steps of B fragments, split like every activation
+    // encoded point: 64 units (63 + a zero) = two k-steps of B fragments, split like every activation; encoded direction: one
+    // k-step.  Each sine / cosine pair is evaluated once per wave (f16p::encode16_wave) and staged through ring slot 2 (and 3):
+    // no DMA targets those before chunk 2 is issued in layer 0, behind the workgroup barrier below, and the compiler's own
+    // waits cover these reads -- the hand-counted waits of the trunk start after that barrier.
+    static_assert(8 * f16p::ENC_STAGE_FLOATS <= (NSL - 2) * CHB * BLOCK_FLOATS, "the staging tiles fit the idle ring slots");
     h16x8 emb_h[2], emb_l[2];
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-        f32x4 q0, q1;
+    h16x8 ed_h, ed_l;
+    {
+        f32x4 eq[4], dq[2];
+#ifdef MVIP_EXPERIMENT_F16W16_NO_ENCODING                                       // timing experiment only (no sin / cos)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-#ifdef MVIP_EXPERIMENT_F16W16_NO_ENCODING                                       // timing experiment only (no sin / cos)
-            q0[i] = px * (float)(i + 1); q1[i] = py * (float)(i + 1);
-#else
-            q0[i] = f16p::enc_channel<63>(px, py, pz, 32 * s + 4 * g + i);
-            q1[i] = f16p::enc_channel<63>(px, py, pz, 32 * s + 16 + 4 * g + i);
-#endif
+            eq[0][i] = eq[2][i] = px * (float)(i + 1); eq[1][i] = eq[3][i] = py * (float)(i + 1);
+            dq[0][i] = vx * (float)(i + 1); dq[1][i] = vy * (float)(i + 1);
         }
-        split_into<0>(q0, emb_h[s], emb_l[s]);
-        split_into<1>(q1, emb_h[s], emb_l[s]);
-        if (s == 0) { stash16(ic<2 * AT_EMB>{}, q0, ic<-1>{}); stash16(ic<2 * AT_EMB + 1>{}, q1, ic<-1>{}); }
-        else { stash16(ic<2 * AT_EMB + 2>{}, q0, ic<-1>{}); stash16(ic<2 * AT_EMB + 3>{}, q1, ic<-1>{}); }
+#else
+        f16p::encode16_wave(lds + 2 * CHB * BLOCK_FLOATS + wave * f16p::ENC_STAGE_FLOATS, lane, px, py, pz, vx, vy, vz, eq, dq);
+#endif
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            split_into<0>(eq[2 * s], emb_h[s], emb_l[s]);
+            split_into<1>(eq[2 * s + 1], emb_h[s], emb_l[s]);
+        }
+        stash16(ic<2 * AT_EMB>{}, eq[0], ic<-1>{}); stash16(ic<2 * AT_EMB + 1>{}, eq[1], ic<-1>{});
+        stash16(ic<2 * AT_EMB + 2>{}, eq[2], ic<-1>{}); stash16(ic<2 * AT_EMB + 3>{}, eq[3], ic<-1>{});
+        split_into<0>(dq[0], ed_h, ed_l);
+        split_into<1>(dq[1], ed_h, ed_l);
+        stash16(ic<2 * AT_EDIR>{}, dq[0], ic<-1>{});
+        stash16(ic<2 * AT_EDIR + 1>{}, dq[1], ic<-1>{});
     }
 
     __syncthreads();                                   // chunks 0, 1 and section B have landed
@@ -413,24 +424,7 @@ mlp_forward_f16x3_w16_kernel(const float *__restrict__ img, const float *__restr
             if constexpr (sg.value == 2) stash16(ic<2 * AT_FEAT + to.value>{}, ev, ic<-1>{});
         });
     // view branch: cat[feature (256), encoded direction (27 + 5)] -> 128, relu; rgb = rgb_linear(v) in the epilogue.
-    // The direction encoding is formed only now (8 fewer live registers through the trunk).
-    h16x8 ed_h, ed_l;
-    {
-        f32x4 q0, q1;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-#ifdef MVIP_EXPERIMENT_F16W16_NO_ENCODING
-            q0[i] = vx * (float)(i + 1); q1[i] = vy * (float)(i + 1);
-#else
-            q0[i] = f16p::enc_channel<27>(vx, vy, vz, 4 * g + i);
-            q1[i] = f16p::enc_channel<27>(vx, vy, vz, 16 + 4 * g + i);
-#endif
-        }
-        split_into<0>(q0, ed_h, ed_l);
-        split_into<1>(q1, ed_h, ed_l);
-        stash16(ic<2 * AT_EDIR>{}, q0, ic<-1>{});
-        stash16(ic<2 * AT_EDIR + 1>{}, q1, ic<-1>{});
-    }
+    // (the direction fragments were formed with the point's in the prologue: one staging pass for both)
     float r0 = 0.f, r1 = 0.f, r2 = 0.f;
     f32x4 w0, w1, w2;
     layer_h<OFF_VIEWS, 8, KS_LV, true, SB_BVIEWS, -1, 8, 2>(st, a0, a1, bias,

@@ -119,15 +119,22 @@ mlp_forward16_kernel(const float *__restrict__ packed, const float *__restrict__
         px = in_a[p * 3]; py = in_a[p * 3 + 1]; pz = in_a[p * 3 + 2];
         vx = in_b[p * 3]; vy = in_b[p * 3 + 1]; vz = in_b[p * 3 + 2];
     }
+    // The encodings are staged through ring slots 2 and 3 (4 KB per wave): no DMA targets them before chunk 2 is issued in
+    // layer 0, behind the workgroup barrier below, and every wave has its fragments in registers when it reaches that barrier.
+    static_assert(NSLOT16 >= 4 && 8 * ENC_STAGE_FLOATS <= 2 * CHUNK_FLOATS, "the staging tiles fit the two idle ring slots");
     f32x4 emb[4], edir[2];
+#ifdef MVIP_EXPERIMENT_NO_ENCODING16               // timing experiment only (no sin / cos, no staging): results are wrong
 #pragma unroll
     for (int t = 0; t < 4; ++t)
 #pragma unroll
-        for (int i = 0; i < 4; ++i) emb[t][i] = enc_channel<63>(px, py, pz, 16 * t + 4 * g + i);
+        for (int i = 0; i < 4; ++i) emb[t][i] = px * (float)(i + 1) + py * (float)t;
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
-        for (int i = 0; i < 4; ++i) edir[t][i] = enc_channel<27>(vx, vy, vz, 16 * t + 4 * g + i);
+        for (int i = 0; i < 4; ++i) edir[t][i] = vx * (float)(i + 1) + vy * (float)t;
+#else
+    encode16_wave(lds + 2 * CHUNK_FLOATS + wave * ENC_STAGE_FLOATS, lane, px, py, pz, vx, vy, vz, emb, edir);
+#endif
 
     // stash: 16-unit tile `t16` (two per 32-unit row tile) of this wave's 16 points -> rows 16 (t16 & 1) + 4 g + i of the
     // block (row tile t16 >> 1, point tile 4 blockIdx + wave / 2), columns 16 (wave & 1) + n.  The block address is
