@@ -787,6 +787,42 @@ int mvip_region_lookup(const float *pts, int64_t P, const float *box, const int 
 int mvip_distortion_loss(const float *rows, int ncols, const float *z, const float *weights, int64_t B, int S, int lindisp,
                          float *loss, float *grad, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Harmonic hole filling of disparity maps and 2D mask dilation (beyond the reference; stands in for
+ * --prepare + LaMa, which produce its Depth_inpainted/ targets; csrc/harmonic.hip, mvip_nerf_amd/prepare.py).
+ * values [N,H,W] fp32, masks [N,H,W] bytes (0 / non-zero), out [N,H,W] fp32 (not values), all DEVICE memory.
+ * Per image: U = masked or non-finite pixels, K the rest, N(p) the 4-neighbours inside the image, deg = |N(p)|;
+ *   for p in U: deg(p) u_p - sum_{q in N(p), q in U} u_q = sum_{q in N(p), q in K} values_q;
+ *   out = values bit for bit on K and u on U.  U empty: out = values, no iteration.  U = the whole image:
+ *   singular, out = values.  Solved by Jacobi-preconditioned conjugate gradients from u = 0, per image
+ *   until r.z <= eps^2 r0.z0; every sum in a fixed order, no float atomics: image n of a batch equals the
+ *   single-image call bit for bit, and a call equals its repetition.
+ * The caller provides workspace (mvip_harmonic_workspace_bytes(N,H,W) bytes, DEVICE) and state [N,16] int32
+ * (DEVICE): word 0 active tiles, 1 unknowns, 2 singular, 3 done, 4 iterations, 5..7 r0.z0 and r.z (fp32 bits),
+ * 8 true residual (fp32 bits), 9 converged.  Nothing is allocated or synchronised inside; the caller reads
+ * state back between the calls.  1 <= H, W <= 16384, N * tiles <= 2^31 - 1; a bad shape (or, with N > 0, a NULL
+ * operand) is MVIP_EINVAL before anything is touched; N == 0: MVIP_OK, nothing launched.
+ * mvip_harmonic_tiles: tiles of 64 x 16 pixels per image (-1 for a bad shape).
+ * mvip_harmonic_setup: marks U, copies values to out, lists each image's active tiles, fills state words 0..4.
+ * mvip_harmonic_init: u = 0, the right-hand side, r0.z0 partials; max_act >= every image's active tile count
+ *   (max_act == 0: nothing launched).
+ * mvip_harmonic_iterate: CG iterations first_iteration .. first_iteration + iterations - 1, two launches each;
+ *   a converged image is frozen (it divides nothing) and sets its done word.  0 <= eps < 1.
+ * mvip_harmonic_finish: state word 8 = max over U of |sum_{N(p)} out_q - deg out_p| / deg, word 9 = converged.
+ * mvip_mask_dilate2d: one round; out = 1 iff any pixel at Chebyshev distance <= 1 is non-zero, clipped at the
+ *   border; masks_out must differ from masks_in. */
+int64_t mvip_harmonic_tiles(int H, int W);
+int64_t mvip_harmonic_workspace_bytes(int64_t N, int H, int W);
+int mvip_harmonic_setup(const float *values, const void *masks, int64_t N, int H, int W, float *out, void *workspace,
+                        int *state, void *stream);
+int mvip_harmonic_init(const float *values, int64_t N, int H, int W, float *out, void *workspace, const int *state,
+                       int64_t max_act, void *stream);
+int mvip_harmonic_iterate(int64_t N, int H, int W, float *out, void *workspace, int *state, int64_t max_act,
+                          int first_iteration, int iterations, float eps, void *stream);
+int mvip_harmonic_finish(int64_t N, int H, int W, const float *out, void *workspace, int *state, int64_t max_act, float eps,
+                         void *stream);
+int mvip_mask_dilate2d(const void *masks_in, int64_t N, int H, int W, void *masks_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

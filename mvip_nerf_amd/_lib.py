@@ -178,6 +178,13 @@ _SIGNATURES = {
     'mvip_region_accumulate': (_int, [_c_f, _c_f, _c_f, _i64, _int, ctypes.POINTER(_flt), ctypes.POINTER(_int), _c_f, _c_f, _c_f]),
     'mvip_region_lookup': (_int, [_c_f, _i64, ctypes.POINTER(_flt), ctypes.POINTER(_int), _c_f, _c_f, _c_f]),
     'mvip_distortion_loss': (_int, [_c_f, _int, _c_f, _c_f, _i64, _int, _int, _c_f, _c_f, _c_f]),
+    'mvip_harmonic_tiles': (_i64, [_int, _int]),
+    'mvip_harmonic_workspace_bytes': (_i64, [_i64, _int, _int]),
+    'mvip_harmonic_setup': (_int, [_c_f, _c_f, _i64, _int, _int, _c_f, _c_f, _c_f, _c_f]),
+    'mvip_harmonic_init': (_int, [_c_f, _i64, _int, _int, _c_f, _c_f, _c_f, _i64, _c_f]),
+    'mvip_harmonic_iterate': (_int, [_i64, _int, _int, _c_f, _c_f, _c_f, _i64, _int, _int, _flt, _c_f]),
+    'mvip_harmonic_finish': (_int, [_i64, _int, _int, _c_f, _c_f, _c_f, _i64, _flt, _c_f]),
+    'mvip_mask_dilate2d': (_int, [_c_f, _i64, _int, _int, _c_f, _c_f]),
 }
 
 # every symbol include/mvip_nerf.h declares; tests check the built library exports all of them

@@ -1973,3 +1973,95 @@ def distortion_loss(weights, z, rows, lindisp=False):
         raise _lib.MvipError(f'distortion_loss: weights on {weights.device}, z on {z.device}, rows on {rows.device}; the HIP '
                              'path has no CPU fallback')
     return _DistortionLoss.apply(_f32c(weights), _f32c(z.detach()), _f32c(rows.detach()), bool(lindisp))
+
+
+# harmonic hole filling and 2D mask dilation (beyond the reference: stands in for --prepare + LaMa; csrc/harmonic.hip) ----------
+
+def _image_batch(what, t, dtype, name):
+    if not torch.is_tensor(t):
+        raise ValueError(f'{what}: {name} must be a tensor on the GPU, got {type(t).__name__}')
+    if t.dtype != dtype:
+        raise ValueError(f'{what}: {name} must be {dtype}, got {t.dtype}')
+    if t.dim() != 3:
+        raise ValueError(f'{what}: {name} must be [N, H, W], got {tuple(t.shape)}')
+    if t.shape[0] > 0 and (t.shape[1] < 1 or t.shape[2] < 1):
+        raise ValueError(f'{what}: empty images {tuple(t.shape)}')
+    return t.detach()
+
+
+def _on_gpu(what, *tensors):
+    if not all(t.is_cuda for t in tensors):
+        raise ValueError(f'{what}: tensors on the GPU expected (the HIP path has no CPU fallback)')
+
+
+def mask_dilate2d(masks, rounds):
+    """masks [N, H, W] bool on the device -> bool: `rounds` rounds of "set iff any pixel at Chebyshev distance <= 1 is set",
+    clipped at the border (the 2D twin of occupancy_dilate).  rounds = 0: a copy."""
+    m = _image_batch('mask_dilate2d', masks, torch.bool, 'masks')
+    rounds = int(rounds)
+    if rounds < 0:
+        raise ValueError(f'mask_dilate2d: rounds must be >= 0, got {rounds}')
+    _on_gpu('mask_dilate2d', m)
+    m = m.contiguous()
+    N, H, W = m.shape
+    cur = m.clone()
+    for _ in range(rounds if N else 0):
+        nxt = torch.empty_like(cur)
+        call('mvip_mask_dilate2d', ptr(cur, torch.bool), N, H, W, ptr(nxt, torch.bool), stream())
+        cur = nxt
+    return cur
+
+
+HARMONIC_STATE_WORDS = 16
+
+
+def harmonic_fill(values, masks, eps=1e-7, max_iters=None, check_every=32):
+    """Fill the masked (and the non-finite) pixels of values [N, H, W] fp32 with the harmonic interpolant of the others: per
+    image the discrete Laplace equation with a mirror boundary at the image border (the definition is csrc/harmonic.hip's
+    and tests/harmonic_numpy.py's), by Jacobi-preconditioned conjugate gradients from zero until r.z <= eps^2 r0.z0.
+    Returns (filled [N, H, W], info); info holds per image numpy arrays `unknowns`, `iterations`, `residual` (the true
+    residual in the max norm, for the record: it stalls near 1e-6 in fp32 while the error still falls), `converged`,
+    `singular` (every pixel unknown: returned unchanged).  Known finite pixels come back bit for bit.  max_iters=None means
+    8 * max(H, W): a cap so that the call always ends (the counts measured are about 2.2 x the hole's diameter).  The flags
+    are read back once every `check_every` iterations.  Detached: no autograd."""
+    import numpy as np
+    v = _image_batch('harmonic_fill', values, _F32, 'values')
+    m = _image_batch('harmonic_fill', masks, torch.bool, 'masks')
+    if tuple(v.shape) != tuple(m.shape) or v.device != m.device:
+        raise ValueError(f'harmonic_fill: values {tuple(v.shape)} on {v.device}, masks {tuple(m.shape)} on {m.device}')
+    if not v.is_contiguous():
+        raise ValueError('harmonic_fill: values must be contiguous')
+    N, H, W = v.shape
+    eps, check_every = float(eps), int(check_every)
+    max_iters = 8 * max(H, W) if max_iters is None else int(max_iters)
+    if not 0.0 <= eps < 1.0 or max_iters < 0 or check_every < 1:
+        raise ValueError(f'harmonic_fill: eps {eps} (0 <= eps < 1), max_iters {max_iters} (>= 0), check_every {check_every} (>= 1)')
+    _on_gpu('harmonic_fill', v, m)
+    m = m.contiguous()
+    out = torch.empty_like(v)
+    if N == 0:
+        e = np.zeros(0, np.int64)
+        return out, {'unknowns': e, 'iterations': e.copy(), 'residual': np.zeros(0, np.float32),
+                     'converged': np.zeros(0, bool), 'singular': np.zeros(0, bool)}
+    nbytes = _lib.load().mvip_harmonic_workspace_bytes(N, H, W)
+    if nbytes < 0:
+        raise ValueError(f'harmonic_fill: {N} images of {H} x {W} are beyond the kernels\' index range')
+    ws = torch.empty(nbytes, device=v.device, dtype=torch.uint8)
+    state = torch.empty((N, HARMONIC_STATE_WORDS), device=v.device, dtype=_I32)
+    st = stream()
+    call('mvip_harmonic_setup', ptr(v), ptr(m, torch.bool), N, H, W, ptr(out), ptr(ws, torch.uint8), ptr(state, _I32), st)
+    max_act = int(state[:, 0].max().cpu())                           # read-back: sizes the launches over the active tiles
+    if max_act > 0:
+        call('mvip_harmonic_init', ptr(v), N, H, W, ptr(out), ptr(ws, torch.uint8), ptr(state, _I32), max_act, st)
+        k = 0
+        while k < max_iters:
+            n = min(check_every, max_iters - k)
+            call('mvip_harmonic_iterate', N, H, W, ptr(out), ptr(ws, torch.uint8), ptr(state, _I32), max_act, k, n, eps, st)
+            k += n
+            if bool(state[:, 3].all().cpu()):                        # read-back: every image is frozen
+                break
+    call('mvip_harmonic_finish', N, H, W, ptr(out), ptr(ws, torch.uint8), ptr(state, _I32), max_act, eps, st)
+    s = state.cpu().numpy()
+    info = {'unknowns': s[:, 1].astype(np.int64), 'iterations': s[:, 4].astype(np.int64),
+            'residual': np.ascontiguousarray(s[:, 8]).view(np.float32).copy(), 'converged': s[:, 9] != 0, 'singular': s[:, 2] != 0}
+    return out, info
