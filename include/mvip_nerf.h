@@ -447,8 +447,10 @@ int mvip_conv3x3_f16x3_ws_moments(const void *xs, const void *packed, const floa
                                   int64_t H, int64_t W, float *y, void *workspace, void *row_moments, int prec,
                                   void *stream);
 /* Unsplit launches (mvip_conv3x3_workspace_bytes == 0, images wider than 8 pixels): the same moments from partials the
- * convolution's epilogue leaves per (image, channel, pixel tile, wave) -- fp32 sums of 64 finished values, added in fp64 in
- * index order by a second, small launch (N * Cout rows) -- instead of a pass over y (DS_NeRF/guidance/sd_utils.py:330-352,
+ * convolution's epilogue leaves per (image, channel, pixel tile, wave) -- fp32 sum and sum of squares of 64 finished values
+ * about a shift (one of the 64 values, kept with them: a row whose mean is many standard deviations loses no variance to
+ * the rounding of raw squares), turned into raw moments and added in fp64 in index order by a second, small launch
+ * (N * Cout rows) -- instead of a pass over y (DS_NeRF/guidance/sd_utils.py:330-352,
  * :390-403: the resnet chains of the VAE encoder and the UNet).  tile_scratch: mvip_conv3x3_tile_moments_scratch_bytes(...)
  * bytes (0 = this shape cannot: use mvip_conv3x3_f16x3_ws / _ws_moments); moments: mvip_groupnorm_workspace_bytes(N, Cout,
  * H * W) bytes in mvip_groupnorm_stats' workspace layout (what mvip_groupnorm_split_planes_moments reads). */

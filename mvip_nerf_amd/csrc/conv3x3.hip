@@ -464,8 +464,9 @@ struct ConvArgs {
     int splits, cks;
     float *partial;
     // GroupNorm moment partials of the OUTPUT from the unsplit epilogue (round 6; null = none): per (image, output channel,
-    // pixel tile, wave) the fp32 sum and sum of squares of the wave's 64 finished values, tile_part[(((n * Cout + co) * tiles
-    // + tile) * 4 + wave) * 2 + {0, 1}]; gn_moments_from_tiles_kernel adds them in fp64 in index order.  The GroupNorm
+    // pixel tile, wave) the fp32 sum and sum of squares of the wave's 64 finished values MINUS a shift K (one of the 64 values)
+    // and K itself, tile_part[(((n * Cout + co) * tiles + tile) * 4 + wave) * 4 + {0, 1, 2}] (word 3 unused);
+    // gn_moments_from_tiles_kernel restores the raw moments and adds them in fp64 in index order.  The GroupNorm
     // that reads y next then needs no pass over y for its statistics (it was gn_moments_kernel: one full read of y).
     float *tile_part;
     int prio;                    // 1: the co-resident workgroups alternate their wave priority stage by stage
@@ -792,15 +793,23 @@ __global__ void __launch_bounds__(NW * 64, (NW == 8 ? (MT <= 2 ? 2 : 1) : (MT <=
                         if (hr) { v0 += rv[m][0][r]; v1 += rv[m][1][r]; }
                         a.y[o0] = v0;
                         a.y[o1] = v1;
-                        float sm = v0 + v1, q = v0 * v0 + v1 * v1;
+                        // Moments about a shift K, the channel's value at the half-wave's first pixel: E[y^2] - mean^2 of a row whose
+                        // mean is 100 standard deviations (residual streams) loses the variance to the fp32 rounding of the raw
+                        // squares (relative error (mean / std)^2 ulps); the deviations from a value of the row itself are of the
+                        // order of the standard deviation, and the reduction restores the raw moments in fp64.
+                        const float k_lo = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v0), 0));
+                        const float k_hi = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v0), 32));
+                        const float K = kg ? k_hi : k_lo;
+                        const float d0 = v0 - K, d1 = v1 - K;
+                        float sm = d0 + d1, q = d0 * d0 + d1 * d1;
                         sm += dpp_f32<0x111>(0.f, sm); q += dpp_f32<0x111>(0.f, q);
                         sm += dpp_f32<0x112>(0.f, sm); q += dpp_f32<0x112>(0.f, q);
                         sm += dpp_f32<0x114>(0.f, sm); q += dpp_f32<0x114>(0.f, q);
                         sm += dpp_f32<0x118>(0.f, sm); q += dpp_f32<0x118>(0.f, q);
                         sm += dpp_f32<0x142, 0xa>(0.f, sm); q += dpp_f32<0x142, 0xa>(0.f, q);
                         if (l32 == 31) {
-                            float2 *dst = reinterpret_cast<float2 *>(a.tile_part) + (((int64_t)n_out * a.Cout + co) * tiles + tile_lin) * 4 + wave;
-                            *dst = make_float2(sm, q);
+                            float4 *dst = reinterpret_cast<float4 *>(a.tile_part) + (((int64_t)n_out * a.Cout + co) * tiles + tile_lin) * 4 + wave;
+                            *dst = make_float4(sm, q, K, 0.f);
                         }
                     }
             }
@@ -909,27 +918,33 @@ cv_split_reduce_moments_kernel(const float *__restrict__ partial, int splits, in
     if (lr == LPR - 1) { moments[row * 2] = sm; moments[row * 2 + 1] = q; }
 }
 
-// GroupNorm moments of a convolution output from the tile partials its unsplit epilogue left (ConvArgs::tile_part): the
-// (image, channel) row's `parts` (sum, sum of squares) pairs added in fp64 and written in the layout gn_moments_kernel leaves
-// for this row length (`chunks` pairs per row: the total in the first, zeros in the rest), which is what
-// cv_to_split_kernel<GN> and gn_finalize_kernel read.
+// GroupNorm moments of a convolution output from the tile partials its unsplit epilogue left (ConvArgs::tile_part): each
+// partial (s, q, K) holds the fp32 sum and sum of squares of 64 values about the shift K, i.e. raw moments s + 64 K and
+// q + 2 K s + 64 K^2, formed here in fp64; the (image, channel) row's `parts` of them added in fp64 and written in the layout
+// gn_moments_kernel leaves for this row length (`chunks` pairs per row: the total in the first, zeros in the rest), which is
+// what cv_to_split_kernel<GN> and gn_finalize_kernel read.
+__device__ __forceinline__ void tile_partial_add(const float4 t, double &sm, double &q) {
+    const double s = (double)t.x, k = (double)t.z;
+    sm += s + 64.0 * k;
+    q += (double)t.y + k * (2.0 * s + 64.0 * k);
+}
+
 __global__ void __launch_bounds__(256)
-gn_moments_from_tiles_kernel(const float2 *__restrict__ part, int parts, int64_t rows, int chunks, double *__restrict__ out) {
+gn_moments_from_tiles_kernel(const float4 *__restrict__ part, int parts, int64_t rows, int chunks, double *__restrict__ out) {
     // one WORKGROUP per row (the first version -- one wave per row, one load in flight per lane -- took 17.6 us per launch at
-    // 4,096 partials per row: as long as the pass over y it replaces): thread t adds partials t, t + 256, ... four at a time,
-    // then the xor tree inside each wave and the four waves in index order -- a fixed order, bit-reproducible
+    // 4,096 partials per row: as long as the pass over y it replaces): thread t adds partials t, t + 256, ... four loads in
+    // flight, then the xor tree inside each wave and the four waves in index order -- a fixed order, bit-reproducible
     __shared__ double red[2][4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t row = blockIdx.x;
-    const float2 *p = part + row * parts;
+    const float4 *p = part + row * parts;
     double sm = 0.0, q = 0.0;
     int i = threadIdx.x;
     for (; i + 768 < parts; i += 1024) {
-        const float2 t0 = p[i], t1 = p[i + 256], t2 = p[i + 512], t3 = p[i + 768];
-        sm += ((double)t0.x + (double)t1.x) + ((double)t2.x + (double)t3.x);
-        q += ((double)t0.y + (double)t1.y) + ((double)t2.y + (double)t3.y);
+        const float4 t0 = p[i], t1 = p[i + 256], t2 = p[i + 512], t3 = p[i + 768];
+        tile_partial_add(t0, sm, q); tile_partial_add(t1, sm, q); tile_partial_add(t2, sm, q); tile_partial_add(t3, sm, q);
     }
-    for (; i < parts; i += 256) { const float2 t = p[i]; sm += (double)t.x; q += (double)t.y; }
+    for (; i < parts; i += 256) tile_partial_add(p[i], sm, q);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) { sm += __shfl_xor(sm, o, 64); q += __shfl_xor(q, o, 64); }
     if (lane == 0) { red[0][wave] = sm; red[1][wave] = q; }
@@ -1922,7 +1937,7 @@ static int conv3x3_launch(const void *xs, const void *packed, const float *bias,
     if (tile_part) {
         const int64_t HW = H * W, rows = N * Cout;
         const int chunks = (int)(mvip_groupnorm_workspace_bytes(1, 1, HW) / 16);
-        hipLaunchKernelGGL(gn_moments_from_tiles_kernel, dim3((unsigned)rows), dim3(256), 0, st, (const float2 *)tile_part,
+        hipLaunchKernelGGL(gn_moments_from_tiles_kernel, dim3((unsigned)rows), dim3(256), 0, st, (const float4 *)tile_part,
                            a.tilesX * a.tilesY * 4, rows, chunks, row_moments);
         return check_launch();
     }
@@ -1974,7 +1989,7 @@ extern "C" int64_t mvip_conv3x3_tile_moments_scratch_bytes(int64_t N, int64_t Ci
     cv_geometry(N, Cout, H, W, tw, MT, blocks);
     if (tw == 8) return 0;
     const int th = 256 / tw;
-    return N * Cout * (W / tw) * (H / th) * 4 * 2 * (int64_t)sizeof(float);
+    return N * Cout * (W / tw) * (H / th) * 4 * 4 * (int64_t)sizeof(float);      // (sum, sum of squares, shift, -) per wave
 }
 
 // The unsplit convolution that ALSO leaves the GroupNorm moments of y (the statistics pass of the GroupNorm that reads y next:

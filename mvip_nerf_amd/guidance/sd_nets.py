@@ -183,15 +183,19 @@ class Transformer2DModel(nn.Module):
                 if transformer_cm.supported(self, x):
                     return transformer_cm.transformer2d_forward(self, x, ctx)
             fast = USE_MFMA_CONV1X1 and ops.conv1x1_supported(self.proj_in, x)       # 1x1 projections on the split-precision GEMM
+        # images too small for either path above (the 4 x 4 level of a 32 x 32 latent): the projections still run on the
+        # split-precision GEMM, columns padded (conv_any) -- the library's 1x1 convolution at 16 pixels is not reproducible from
+        # one call to the next (its outputs moved by 4e-7 between identical calls on an MI355X)
+        proj = conv_any if USE_MFMA_CONV1X1 else (lambda conv, t: conv(t))
         if fast:
             h = ops.norm_conv1x1(x, self.norm, self.proj_in).permute(0, 2, 1)
         else:
-            h = self.proj_in(self.norm(x)).permute(0, 2, 3, 1).reshape(B, H * W, C)
+            h = proj(self.proj_in, self.norm(x)).permute(0, 2, 3, 1).reshape(B, H * W, C)
         for blk in self.transformer_blocks:
             h = blk(h, ctx)
         if fast:
             return ops.tokens_conv1x1(h, self.proj_out, x)
-        return x + self.proj_out(h.reshape(B, H, W, C).permute(0, 3, 1, 2))
+        return x + proj(self.proj_out, h.reshape(B, H, W, C).permute(0, 3, 1, 2))
 
 
 class Downsample2D(nn.Module):

@@ -4,11 +4,16 @@ against an explicit eager loop, and the public methods' determinism / shapes / s
 import ctypes
 import copy
 import math
+import os
+import sys
 
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from sd_network_cases import library_kernels_in                        # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -199,9 +204,7 @@ def test_decode_latents_launches_no_library_kernel(sd, cuda):
         sd.decode_latents(z)
         torch.cuda.synchronize()
     names = [e.key for e in prof.key_averages()]
-    banned = ('igemm', 'miopen', 'naive_conv', 'Im2d2Col', 'Col2Im', 'batched_transpose', 'Cijk_', 'attn_fwd', 'ck::',
-              'grouped_conv', 'MIOpen', 'gemm_kernel', 'softmax_warp', 'SoftMax', 'upsample_nearest')
-    assert not [n for n in names if any(b in n for b in banned)], [n for n in names if any(b in n for b in banned)]
+    assert not library_kernels_in(names), library_kernels_in(names)     # the banned names: tests/sd_network_cases.py
     for must in ('vae_decoder_head_kernel', 'conv3x3_f16x3_kernel'):
         assert any(must in n for n in names), must
 
