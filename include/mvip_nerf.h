@@ -825,6 +825,29 @@ int mvip_harmonic_finish(int64_t N, int H, int W, const float *out, void *worksp
                          void *stream);
 int mvip_mask_dilate2d(const void *masks_in, int64_t N, int H, int W, void *masks_out, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Reference-view propagation: backward depth warping (beyond the reference, which has no counterpart: its
+ * RGB_inpainted/ images are independent 2D inpaintings; csrc/warp.hip, ops.warp_views,
+ * prepare.propagate_reference).  All operands DEVICE memory, dense:
+ *   tgt_disp [N,H,W] fp32, tgt_pose [N,3,4] (camera-to-world, get_rays' convention), tgt_mask [N,H,W] bytes
+ *   (0 / non-zero: the pixels to compute); src_rgb [S,H,W,3], src_disp [S,H,W], src_pose [S,3,4];
+ *   order [N,S] int32: per target the sources in order of preference, an entry outside [0,S) is skipped.
+ * A masked target pixel with a finite disparity > 0 is lifted to its world point at planar depth 1/disp and
+ * projected into each source of its order row in turn; the source's disparity d_s and colour are read
+ * bilinearly (taps x0 = min(floor(u), W-2), y0 = min(floor(v), H-2)); the first source with t_s > 0,
+ * 0 <= u <= W-1, 0 <= v <= H-1, d_s finite and > 0, |t_s d_s - 1| <= tol and finite colours is taken (the
+ * operation order is written out in csrc/warp.hip and tests/warp_numpy.py).
+ *   rgb [N,H,W,3], index [N,H,W] int32 (the source, or -1), resid [N,H,W] (t_s d_s - 1); every pixel of every
+ *   target is written: 0 / -1 / 0 where the pixel is unmasked, invalid, or no source is taken.
+ * One launch, one thread per target pixel, a pure gather: no atomics, every index bounded in the kernel, a
+ * pixel's result independent of the rest of the batch (bit-reproducible).  2 <= H, W <= 16384, N, S >= 0,
+ * N * ceil(W/64) * ceil(H/4) <= 2^31 - 1, focal and tol finite and > 0, else MVIP_EINVAL before anything is
+ * touched; N == 0: MVIP_OK, nothing launched; with N > 0 a NULL target or output operand is MVIP_EINVAL, and
+ * so is a NULL source operand or order unless S == 0 (then every pixel gets 0 / -1 / 0). */
+int mvip_warp_views(const float *tgt_disp, const float *tgt_pose, const void *tgt_mask, int64_t N, int H, int W,
+                    const float *src_rgb, const float *src_disp, const float *src_pose, int S, const int *order,
+                    float focal, float tol, float *rgb, int *index, float *resid, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -185,6 +185,7 @@ _SIGNATURES = {
     'mvip_harmonic_iterate': (_int, [_i64, _int, _int, _c_f, _c_f, _c_f, _i64, _int, _int, _flt, _c_f]),
     'mvip_harmonic_finish': (_int, [_i64, _int, _int, _c_f, _c_f, _c_f, _i64, _flt, _c_f]),
     'mvip_mask_dilate2d': (_int, [_c_f, _i64, _int, _int, _c_f, _c_f]),
+    'mvip_warp_views': (_int, [_c_f, _c_f, _c_f, _i64, _int, _int, _c_f, _c_f, _c_f, _int, _c_f, _flt, _flt, _c_f, _c_f, _c_f, _c_f]),
 }
 
 # every symbol include/mvip_nerf.h declares; tests check the built library exports all of them

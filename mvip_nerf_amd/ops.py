@@ -2065,3 +2065,65 @@ def harmonic_fill(values, masks, eps=1e-7, max_iters=None, check_every=32):
     info = {'unknowns': s[:, 1].astype(np.int64), 'iterations': s[:, 4].astype(np.int64),
             'residual': np.ascontiguousarray(s[:, 8]).view(np.float32).copy(), 'converged': s[:, 9] != 0, 'singular': s[:, 2] != 0}
     return out, info
+
+
+# reference-view propagation: backward depth warping (beyond the reference, which has no counterpart; csrc/warp.hip) --------------
+
+def _pose_batch(what, t, name):
+    if not torch.is_tensor(t):
+        raise ValueError(f'{what}: {name} must be a tensor on the GPU, got {type(t).__name__}')
+    if t.dtype != _F32:
+        raise ValueError(f'{what}: {name} must be {_F32}, got {t.dtype}')
+    if t.dim() != 3 or tuple(t.shape[1:]) != (3, 4):
+        raise ValueError(f'{what}: {name} must be [N, 3, 4], got {tuple(t.shape)}')
+    return t.detach()
+
+
+def warp_views(tgt_disp, tgt_pose, tgt_mask, src_rgb, src_disp, src_pose, focal, order=None, tol=0.05):
+    """Backward depth warp of S source views into N target views (the definition is csrc/warp.hip's and tests/warp_numpy.py's).
+    tgt_disp [N, H, W] fp32, tgt_pose [N, 3, 4], tgt_mask [N, H, W] bool (the pixels to compute); src_rgb [S, H, W, 3],
+    src_disp [S, H, W], src_pose [S, 3, 4]; order [N, S] int32: per target the sources in order of preference (None: ascending
+    index), an entry outside [0, S) is skipped.  A masked pixel with a finite disparity > 0 takes the first source in which it
+    projects inside the image, in front of the camera, and onto a surface at its own depth: |t_s d_s - 1| <= tol (0.05 sits above
+    the step of 8-bit disparity rasters, 0.5 to 3 % of their value).  Returns (rgb [N, H, W, 3], index [N, H, W] int32: the
+    source or -1, resid [N, H, W]); 0 / -1 / 0 where nothing is taken.  One launch.  Detached: no autograd."""
+    what = 'warp_views'
+    d = _image_batch(what, tgt_disp, _F32, 'tgt_disp')
+    m = _image_batch(what, tgt_mask, torch.bool, 'tgt_mask')
+    sd = _image_batch(what, src_disp, _F32, 'src_disp')
+    tp, sp = _pose_batch(what, tgt_pose, 'tgt_pose'), _pose_batch(what, src_pose, 'src_pose')
+    if not torch.is_tensor(src_rgb) or src_rgb.dtype != _F32 or src_rgb.dim() != 4 or src_rgb.shape[-1] != 3:
+        got = f'{tuple(src_rgb.shape)} {src_rgb.dtype}' if torch.is_tensor(src_rgb) else type(src_rgb).__name__
+        raise ValueError(f'{what}: src_rgb must be a {_F32} tensor [S, H, W, 3] on the GPU, got {got}')
+    sc = src_rgb.detach()
+    N, H, W = d.shape
+    S = sd.shape[0]
+    if tuple(m.shape) != (N, H, W) or tp.shape[0] != N:
+        raise ValueError(f'{what}: tgt_disp {tuple(d.shape)}, tgt_mask {tuple(m.shape)}, tgt_pose {tuple(tp.shape)}: one N, H, W expected')
+    if tuple(sd.shape[1:]) != (H, W) or tuple(sc.shape) != (S, H, W, 3) or sp.shape[0] != S:
+        raise ValueError(f'{what}: src_disp {tuple(sd.shape)}, src_rgb {tuple(sc.shape)}, src_pose {tuple(sp.shape)} for targets of '
+                         f'{H} x {W}: one S, and the targets\' H, W expected')
+    if H < 2 or W < 2:
+        raise ValueError(f'{what}: images of at least 2 x 2 expected, got {H} x {W}')
+    focal, tol = float(focal), float(tol)
+    if not (0.0 < focal < float('inf') and 0.0 < tol < float('inf')):
+        raise ValueError(f'{what}: focal {focal} and tol {tol} must be finite and > 0')
+    tensors = [d, tp, m, sc, sd, sp]
+    if order is not None:
+        if not torch.is_tensor(order) or order.dtype != _I32 or tuple(order.shape) != (N, S):
+            got = f'{tuple(order.shape)} {order.dtype}' if torch.is_tensor(order) else type(order).__name__
+            raise ValueError(f'{what}: order must be an {_I32} tensor [{N}, {S}] on the GPU, got {got}')
+        tensors.append(order.detach())
+    _on_gpu(what, *tensors)
+    if any(t.device != d.device for t in tensors):
+        raise ValueError(f'{what}: tensors on one device expected, got {sorted({str(t.device) for t in tensors})}')
+    if not all(t.is_contiguous() for t in tensors):
+        raise ValueError(f'{what}: every operand must be contiguous')
+    if order is None:
+        order = torch.arange(S, device=d.device, dtype=_I32).repeat(N, 1).reshape(N, S)
+    rgb = torch.empty((N, H, W, 3), device=d.device, dtype=_F32)
+    index = torch.empty((N, H, W), device=d.device, dtype=_I32)
+    resid = torch.empty((N, H, W), device=d.device, dtype=_F32)
+    call('mvip_warp_views', ptr(d), ptr(tp), ptr(m, torch.bool), N, H, W, ptr(sc), ptr(sd), ptr(sp), S, ptr(order.detach(), _I32),
+         focal, tol, ptr(rgb), ptr(index, _I32), ptr(resid), stream())
+    return rgb, index, resid

@@ -14,6 +14,10 @@ pixels OUTSIDE the masks are kept: the rendered part of `filled` supervises, the
 `'masked'` (SPIn-NeRF's reading) only the pixels inside the masks are kept -- exactly the filled part -- and `'all'` keeps
 both.  `prepare_depths(...)['filled'].cpu().numpy()` goes into `scene.LLFFScene(..., inpainted_depths=...)` as it is and
 keeps the precision that the 8-bit PNG of `write_llff` drops (one step of 1 / 255).
+
+The third raster, `RGB_inpainted/`, comes from `propagate_reference`: one inpainted view (or a few) is
+carried into every other view by backward depth warping (`ops.warp_views`), what no reference sees is filled harmonically,
+and `write_images` writes the files.
 """
 import os
 
@@ -95,4 +99,110 @@ def write_llff(root, names, masks, depths):
     for i, name in enumerate(names):
         run._write_png(os.path.join(root, 'label', name + '.png'), grey(m8[i]))
         run._write_png(os.path.join(root, 'Depth_inpainted', name + '.png'), grey(d8[i]))
+    return clipped
+
+
+# ---- reference-view propagation: the RGB_inpainted/ images from one inpainted view (or a few) ---------------------------------------
+
+def _to_device(a, device, dtype):
+    t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
+    return t.detach().to(device=device, dtype=dtype).contiguous()
+
+
+def reference_order(poses, ref_views):
+    """int32 [N, R]: per view the positions in ref_views ordered by the distance between the camera centres (fp64 on the host),
+    ties by position."""
+    c = np.asarray(poses, np.float64)[:, :3, 3]
+    dist = np.linalg.norm(c[:, None, :] - c[None, list(ref_views), :], axis=-1)
+    return np.argsort(dist, axis=1, kind='stable').astype(np.int32)
+
+
+def propagate_reference(images, masks, disparities, poses, focal, ref_views, ref_images=None, tol=0.05, fill=True, **fill_kw):
+    """Carry the inpainted reference views into every other view through geometry (beyond the reference, whose RGB_inpainted/
+    images are independent 2D inpaintings): each masked pixel is lifted with its own disparity and looks its colour up in
+    the nearest reference view that sees the same surface (ops.warp_views; the definition is csrc/warp.hip's).
+
+    images [N, H, W, 3] fp32 in 0..1, masks [N, H, W] bool, disparities [N, H, W] (the field's: prepare_depths(...)['filled'];
+    or the dataset's rasters; nothing is rendered here), poses [N, 3, 4], ref_views: indices of the inpainted views,
+    ref_images [R, H, W, 3]: their inpainted images (None: images[ref_views]).  Tensors or arrays; the work is done on the
+    device of `images` when that is a GPU tensor, else on 'cuda'.
+
+    Per target the references are tried in the order of reference_order.  The output image is `images` outside the mask bit
+    for bit, the warped colour where a reference was taken, and on the remaining masked pixels (holes) the harmonic
+    interpolant of the pixels around them, per channel, by one ops.harmonic_fill call over [3N, H, W] (fill=False leaves
+    `images` there; fill_kw: eps, max_iters, check_every, and allow_unconverged as in prepare_depths).  A view that is itself a
+    reference takes its reference image unchanged (its masked pixels name itself as the source).
+
+    Returns dict(images [N, H, W, 3], source [N, H, W] int32: -1 or the position in ref_views, resid [N, H, W], holes
+    [N, H, W] bool = masks & (source < 0), coverage: numpy [N], the share of each view's masked pixels with a source (1 for
+    an empty mask), info: ops.harmonic_fill's over the planes 3 n + channel, None without fill).  ValueError for mismatched
+    shapes, an empty or invalid ref_views, and a plane with nothing to interpolate from; RuntimeError naming the views whose
+    fill did not converge, unless allow_unconverged."""
+    allow_unconverged = bool(fill_kw.pop('allow_unconverged', False))
+    device = images.device if torch.is_tensor(images) and images.is_cuda else torch.device('cuda')
+    shape = lambda a: tuple(a.shape) if hasattr(a, 'shape') else type(a).__name__
+    if len(shape(images)) != 4 or shape(images)[-1] != 3:
+        raise ValueError(f'propagate_reference: images [N, H, W, 3] expected, got {shape(images)}')
+    N, H, W, _ = shape(images)
+    if shape(masks) != (N, H, W) or shape(disparities) != (N, H, W):
+        raise ValueError(f'propagate_reference: masks {shape(masks)} and disparities {shape(disparities)} for images {shape(images)}: '
+                         f'[{N}, {H}, {W}] expected')
+    poses_t = _poses(poses)
+    if poses_t.shape[0] != N:
+        raise ValueError(f'propagate_reference: {poses_t.shape[0]} poses for {N} images')
+    refs = [int(v) for v in ref_views]
+    if not refs or len(set(refs)) != len(refs) or min(refs) < 0 or max(refs) >= N:
+        raise ValueError(f'propagate_reference: ref_views {refs}: at least one view of 0..{N - 1}, each once, expected')
+    if ref_images is not None and shape(ref_images) != (len(refs), H, W, 3):
+        raise ValueError(f'propagate_reference: ref_images {shape(ref_images)}: [{len(refs)}, {H}, {W}, 3] expected')
+    img = _to_device(images, device, torch.float32)
+    msk = (torch.as_tensor(np.asarray(masks) if not torch.is_tensor(masks) else masks) != 0).to(device).contiguous()
+    disp = _to_device(disparities, device, torch.float32)
+    pose = _to_device(poses_t, device, torch.float32)
+    ridx = torch.as_tensor(refs, device=device, dtype=torch.int64)
+    src_rgb = _to_device(ref_images, device, torch.float32) if ref_images is not None else img[ridx].contiguous()
+    order = torch.from_numpy(reference_order(pose.cpu().numpy(), refs)).to(device)
+    warp_mask = msk.clone()
+    warp_mask[ridx] = False                                   # a reference view is not warped into
+    rgb, source, resid = ops.warp_views(disp, pose, warp_mask, src_rgb, disp[ridx].contiguous(), pose[ridx].contiguous(),
+                                        float(focal), order=order.contiguous(), tol=tol)
+    out = torch.where((source >= 0)[..., None], rgb, img)
+    for k, v in enumerate(refs):
+        out[v] = src_rgb[k]
+        source[v] = torch.where(msk[v], k, -1).to(source.dtype)
+    holes = msk & (source < 0)
+    info = None
+    if fill:
+        planes = out.permute(0, 3, 1, 2).reshape(3 * N, H, W).contiguous()
+        filled, info = ops.harmonic_fill(planes, holes[:, None].expand(N, 3, H, W).reshape(3 * N, H, W).contiguous(), **fill_kw)
+        singular = sorted({int(p) // 3 for p in np.nonzero(info['singular'])[0]})
+        if singular:
+            raise ValueError(f'propagate_reference: views {singular} have no known pixel to fill their holes from')
+        bad = sorted({int(p) // 3 for p in np.nonzero(~info['converged'])[0]})
+        if bad and not allow_unconverged:
+            raise RuntimeError(f'propagate_reference: the fill of views {bad} did not converge (raise max_iters, or pass '
+                               f'allow_unconverged=True)')
+        out = torch.where(holes[..., None], filled.reshape(N, 3, H, W).permute(0, 2, 3, 1), out)
+    n_mask = msk.sum((1, 2)).cpu().numpy().astype(np.float64)
+    n_src = (msk & (source >= 0)).sum((1, 2)).cpu().numpy().astype(np.float64)
+    coverage = np.where(n_mask > 0, n_src / np.maximum(n_mask, 1.0), 1.0)
+    return {'images': out.contiguous(), 'source': source, 'resid': resid, 'holes': holes, 'coverage': coverage, 'info': info}
+
+
+def write_images(root, names, images):
+    """Write root/RGB_inpainted/NAME.png (round(clip(v, 0, 1) * 255)): the images load_llff._load_data reads.  images
+    [N, H, W, 3] (tensor or array).  Returns the number of values that were clipped (outside [0, 1], or not finite: written
+    as 0)."""
+    from . import run
+    images = images.detach().cpu().numpy() if torch.is_tensor(images) else np.asarray(images)
+    names = list(names)
+    if images.ndim != 4 or images.shape[-1] != 3 or images.shape[0] != len(names):
+        raise ValueError(f'images {images.shape} for {len(names)} names: [N, H, W, 3] expected')
+    os.makedirs(os.path.join(root, 'RGB_inpainted'), exist_ok=True)
+    v = images.astype(np.float64)
+    finite = np.isfinite(v)
+    clipped = int((~finite | (v < 0) | (v > 1)).sum())
+    v8 = np.round(np.clip(np.where(finite, v, 0.0), 0.0, 1.0) * 255.0).astype(np.uint8)
+    for i, name in enumerate(names):
+        run._write_png(os.path.join(root, 'RGB_inpainted', name + '.png'), np.ascontiguousarray(v8[i]))
     return clipped

@@ -88,6 +88,7 @@ class SecondStageTrainer:
         self.rng = np.random.RandomState(1234)         # same draw on every rank (view choice must agree)
         self.N_rand = args.N_rand
         self.last_distortion = None                    # the step's distortion term (detached scalar), None when off
+        self.last_reference = None                     # the step's reference term (detached scalar), None when off
         # one flat bucket, reduced as two asynchronous halves [coarse network | fine network] (dist_utils.OverlappedGradBuckets);
         # MVIP_OVERLAP_ALLREDUCE=0 restores the single blocking all_reduce after the backward (A/B switch, same values)
         n_coarse = len(list(self.kw_train['network_fn'].parameters())) if self.kw_train.get('network_fn') is not None else 0
@@ -292,6 +293,25 @@ class SecondStageTrainer:
             # iteration to have the reference's cost structure: a plain colour loss stands in
             wm = sel.numel() / max(masked_idx.numel(), 1)
             loss = loss + args.sds_loss_weight * img2mse(rgb_masked, sc.images[img_i].reshape(-1, 3)[sel]) * wm
+        # reference term (extension, default off: args.reference_lambda absent or 0 leaves the step as it is): next to a diffusion
+        # prior, the masked render is also held to the scene's images inside the masks -- prepare.propagate_reference's output when
+        # the scene was built from it -- in the form and with the shard weighting of the stand-in above, on the render the step
+        # already has.  scene.reference_valid [N, H, W] bool (None: every masked pixel) keeps harmonically filled holes out.
+        self.last_reference = None
+        ref_lambda = float(getattr(args, 'reference_lambda', 0.) or 0.)
+        if ref_lambda > 0 and self.guidance is not None:
+            target_ref = sc.images[img_i].reshape(-1, 3)[sel]
+            valid = getattr(sc, 'reference_valid', None)
+            if valid is None:
+                ref = img2mse(rgb_masked, target_ref) * (sel.numel() / max(masked_idx.numel(), 1)) if sel.numel() else None
+            else:
+                # mean over the view's valid masked pixels, this rank's share of the sum (no read-back; all false: exactly zero)
+                valid = valid[img_i].reshape(-1)
+                n_valid = valid[masked_idx].sum().clamp(min=1).to(rgb_masked.dtype)
+                ref = (((rgb_masked - target_ref) ** 2).sum(-1) * valid[sel].to(rgb_masked.dtype)).sum() / (3. * n_valid)
+            if ref is not None:
+                self.last_reference = (ref_lambda * ref).detach()
+                loss = loss + ref_lambda * ref
         # ray distortion loss of the two supervision renders (mip-NeRF 360 eq. 15; the masked SDS render and the neighbour views
         # are not regularised), shard means weighted like the terms above, empty shards skipped
         self.last_distortion = None

@@ -1,0 +1,152 @@
+"""Reference-view propagation (mvip_nerf_amd/prepare.py): carry one inpainted view (or a few) into every other view by backward
+depth warping, fill what no reference sees harmonically, write the RGB_inpainted/ images the loader reads.
+
+  python tools/propagate_reference.py --fixture [--ref-views 0] [--tol 0.05] --out DIR
+  python tools/propagate_reference.py --datadir SCENE [--factor 4] --ref-views 0,30 [--ref-image A.png --ref-image B.png] --out DIR
+  ... --depths field --checkpoint CKPT.tar      (the field's disparities, prepare.prepare_depths, instead of the dataset's rasters)
+
+--fixture uses tests/golden/scene1_small.npz (images, masks, 8-bit disparity rasters, poses); --datadir a SPIn-NeRF style scene
+with its RGB_inpainted/, label/ and Depth_inpainted/.  --ref-image replaces the image of a reference view, in the order of
+--ref-views (a 2D inpainting made elsewhere); without it the scene's own image of that view is the reference.  --depths field
+renders the disparities from a model instead (--checkpoint in the reference's .tar format; with --fixture and no checkpoint
+the 1,500-iteration recipe of tools/render_occupancy_ab.py::train_scene1 is trained first) and fills them inside the masks.
+
+Into DIR: RGB_inpainted/NAME.png, source.npy (int32 [N, H, W]: -1 or the position in --ref-views), and one JSON (printed, and
+DIR/reference_propagation.json): per view the coverage (share of the masked pixels that found a reference), the RMS inside the
+mask against the scene's own images (all masked pixels, and the warped ones alone), the same for the baseline that fills the
+whole mask harmonically, a sweep over tol, and seconds per stage.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+SWEEP = (0.01, 0.02, 0.05, 0.1, 0.2)
+
+
+def rms(a, b, sel):
+    return float(np.sqrt(((a[sel].astype(np.float64) - b[sel]) ** 2).mean())) if sel.any() else None
+
+
+def load_scene(a, dev):
+    """(images [N,H,W,3], masks, dataset disparities, poses [N,3,4], (H, W, focal), names, near, far) as numpy."""
+    if a.fixture:
+        z = np.load(os.path.join(ROOT, 'tests', 'golden', 'scene1_small.npz'), allow_pickle=False)
+        images = z['images'].astype(np.float32) / np.float32(255.)
+        H, W = images.shape[1:3]
+        focal = float(z['poses'][0, 2, 4]) * W / float(z['poses'][0, 1, 4])
+        names = ['{:06d}'.format(i) for i in range(len(images))]
+        return images, z['masks'].astype(bool), z['depths'].astype(np.float32) / np.float32(255.), \
+            np.ascontiguousarray(z['poses'][:, :, :4]), (H, W, focal), names, float(z['bds'].min() * .9), float(z['bds'].max())
+    from mvip_nerf_amd.load_llff import load_llff_data
+    images, poses, bds, _, _, masks, depths, mask_indices = load_llff_data(a.datadir, factor=a.factor)
+    if len(mask_indices) != len(images):
+        raise SystemExit(f'{a.datadir}: {len(mask_indices)} masks for {len(images)} views: one per view expected')
+    H, W, focal = (float(v) for v in poses[0, :3, -1])
+    root = os.path.join(a.datadir, 'images' if a.factor is None else f'images_{a.factor}', 'RGB_inpainted')
+    names = [f.split('.')[0] for f in sorted(os.listdir(root)) if f.endswith(('JPG', 'jpg', 'jpeg', 'png'))]
+    return images.astype(np.float32), masks == 1, depths.astype(np.float32), np.ascontiguousarray(poses[:, :3, :4]).astype(np.float32), \
+        (int(H), int(W), focal), names, float(bds.min() * .9), float(bds.max())
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    ap.add_argument('--fixture', action='store_true')
+    ap.add_argument('--datadir')
+    ap.add_argument('--factor', type=int, default=4)
+    ap.add_argument('--ref-views', default='0', help='the inpainted views, comma separated (default 0)')
+    ap.add_argument('--ref-image', action='append', default=[], metavar='PNG',
+                    help='the inpainted image of a reference view, in the order of --ref-views; may be repeated')
+    ap.add_argument('--tol', type=float, default=0.05, help='relative depth tolerance of the visibility test')
+    ap.add_argument('--depths', choices=('dataset', 'field'), default='dataset')
+    ap.add_argument('--checkpoint', help='model for --depths field')
+    ap.add_argument('--iters', type=int, default=1500, help='training iterations of --fixture --depths field without a checkpoint')
+    ap.add_argument('--out', required=True)
+    a = ap.parse_args(argv)
+    if a.fixture == bool(a.datadir):
+        ap.error('either --fixture or --datadir')
+    if a.depths == 'field' and not a.fixture and not a.checkpoint:
+        ap.error('--depths field needs --checkpoint (or --fixture)')
+    refs = [int(v) for v in a.ref_views.split(',') if v != '']
+    if len(a.ref_image) > len(refs):
+        ap.error('more --ref-image than --ref-views')
+    from mvip_nerf_amd import load_llff, ops, prepare
+    dev = torch.device('cuda', 0)
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return out, time.perf_counter() - t0
+
+    (images, masks, data_disp, poses, hwf, names, near, far), t_load = timed(lambda: load_scene(a, dev))
+    N, H, W = masks.shape
+    seconds = {'load': t_load}
+    disp = torch.from_numpy(data_disp).to(dev)
+    if a.depths == 'field':
+        if a.checkpoint:
+            from tools.extract_mesh import load_model
+            (kw, _), seconds['model'] = timed(lambda: load_model(a.checkpoint, 'mlp', dev))
+            te = dict(kw, near=near, far=far)
+        else:
+            from tools import render_occupancy_ab as T
+            scene, seconds['model'] = timed(lambda: T.train_scene1(dev, a.iters))
+            te = scene['te']
+        out, seconds['depths'] = timed(lambda: prepare.prepare_depths(te, hwf, torch.from_numpy(poses).to(dev), masks, near, far))
+        disp = out['filled']
+    ref_images = images[refs].copy()
+    for k, path in enumerate(a.ref_image):
+        png = load_llff._imread(path)[..., :3].astype(np.float32) / np.float32(255.)
+        if png.shape != (H, W, 3):
+            raise SystemExit(f'{path}: {png.shape[0]} x {png.shape[1]}, the scene is {H} x {W}')
+        ref_images[k] = png
+    img_t, msk_t, pose_t = torch.from_numpy(images).to(dev), torch.from_numpy(masks).to(dev), torch.from_numpy(poses).to(dev)
+    run = lambda tol, fill: prepare.propagate_reference(img_t, msk_t, disp, pose_t, hwf[2], refs, ref_images=ref_images, tol=tol, fill=fill)
+    _, seconds['warp_and_fill_first_call'] = timed(lambda: run(a.tol, True))
+    res, seconds['warp_and_fill'] = timed(lambda: run(a.tol, True))
+    _, seconds['warp'] = timed(lambda: run(a.tol, False))
+    got, source = res['images'].cpu().numpy(), res['source'].cpu().numpy()
+    os.makedirs(a.out, exist_ok=True)
+    clipped, seconds['write'] = timed(lambda: prepare.write_images(a.out, names, got))
+    np.save(os.path.join(a.out, 'source.npy'), source)
+    # the baseline: no reference at all, the whole mask filled harmonically per channel
+    planes = img_t.permute(0, 3, 1, 2).reshape(3 * N, H, W).contiguous()
+    (base, _), seconds['baseline_fill'] = timed(lambda: ops.harmonic_fill(planes, msk_t[:, None].expand(N, 3, H, W).reshape(3 * N, H, W).contiguous()))
+    base = base.reshape(N, 3, H, W).permute(0, 2, 3, 1).cpu().numpy()
+    others = [v for v in range(N) if v not in refs]
+    warped = masks & (source >= 0)
+    per_view = lambda img, sel: [rms(img[v], images[v], sel[v]) for v in range(N)]
+    mean = lambda xs: float(np.mean([x for v, x in enumerate(xs) if v in others and x is not None])) if others else None
+    in_mask, in_warped, baseline = per_view(got, masks), per_view(got, warped), per_view(base, masks)
+    sweep = []
+    for tol in SWEEP:
+        r = run(tol, True)
+        g, s = r['images'].cpu().numpy(), r['source'].cpu().numpy()
+        sweep.append({'tol': tol, 'mean_coverage': float(np.mean(r['coverage'][others])) if others else None,
+                      'min_coverage': float(np.min(r['coverage'][others])) if others else None,
+                      'mean_rms_in_mask': mean(per_view(g, masks)), 'mean_rms_warped_pixels': mean(per_view(g, masks & (s >= 0)))})
+    out = {'scene': 'tests/golden/scene1_small.npz' if a.fixture else a.datadir, 'frame': [H, W], 'views': N, 'ref_views': refs,
+           'ref_images': a.ref_image, 'depths': a.depths, 'tol': a.tol, 'mask_share_of_frame': float(masks.mean()),
+           'coverage_per_view': [float(c) for c in res['coverage']], 'holes_per_view': res['holes'].sum((1, 2)).cpu().tolist(),
+           'rms_in_mask_per_view': in_mask, 'rms_warped_pixels_per_view': in_warped, 'rms_baseline_harmonic_fill_per_view': baseline,
+           'mean_over_non_reference_views': {'coverage': float(np.mean(res['coverage'][others])) if others else None,
+                                             'rms_in_mask': mean(in_mask), 'rms_warped_pixels': mean(in_warped),
+                                             'rms_baseline_harmonic_fill': mean(baseline)},
+           'note': 'RMS in 0..1 against the scene\'s own images (independent 2D inpaintings of every view) inside the masks',
+           'fill_iterations_max': int(res['info']['iterations'].max()), 'clipped_values': clipped, 'tol_sweep': sweep, 'seconds': seconds}
+    print(json.dumps(out, indent=1))
+    json.dump(out, open(os.path.join(a.out, 'reference_propagation.json'), 'w'), indent=1)
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())
