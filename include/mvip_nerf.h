@@ -848,6 +848,34 @@ int mvip_warp_views(const float *tgt_disp, const float *tgt_pose, const void *tg
                     const float *src_rgb, const float *src_disp, const float *src_pose, int S, const int *order,
                     float focal, float tol, float *rgb, int *index, float *resid, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Structural similarity (SSIM, Wang et al. 2004) with its gradient (beyond the reference: DS_NeRF/evaluation.py
+ * takes its metrics from pyiqa, so there is no reference call site this replaces; csrc/ssim.hip, ops.ssim,
+ * mvip_nerf_amd/evaluate.py, the trainer's reference_ssim_lambda).  All operands DEVICE memory, dense:
+ *   x, y [N,H,W,C] fp32 channel-last, C in 1..4; mask [N,H,W] bytes (0 / non-zero) or NULL (every pixel).
+ * Window: 11 taps g_k ~ exp(-(k-5)^2 / (2 1.5^2)), normalised in fp64 and rounded to fp32, separable, "valid"
+ * extent: the map is [N,H-10,W-10,C] and map pixel (i,j) is centred on image pixel (i+5,j+5).  Per channel, with
+ * mu the windowed means and sigma the biased window-weighted second moments from raw moments,
+ *   s = (2 mu_x mu_y + C1)(2 sigma_xy + C2) / ((mu_x^2 + mu_y^2 + C1)(sigma_x^2 + sigma_y^2 + C2)),
+ * C1 = 1e-4, C2 = 9e-4 (data range 1); no luminance conversion and no downsampling (not pyiqa's Y-channel
+ * preprocessing).  A map pixel counts iff the mask is set at its centre; count[n] = counted map pixels,
+ * ssim[n] = mean of s over counted pixels and channels; count[n] == 0: ssim[n] = 1 exactly.  The operation order
+ * is written out in csrc/ssim.hip and tests/ssim_numpy.py.
+ * mvip_ssim_tiles: map tiles of 32 x 16 per image = workgroups per image of the forward (-1 for a bad shape).
+ * mvip_ssim_forward: two launches (tiles; a fixed-order fp64 reduction per image).  map [N,H-10,W-10,C] or NULL;
+ *   stash [3,N,H-10,W-10,C] or NULL: the planes mvip_ssim_backward reads; partials [N*tiles] fp64 and
+ *   partial_counts [N*tiles] int32: workspace; ssim [N] fp32, count [N] int32.
+ * mvip_ssim_backward: one launch, a gather per image pixel (no atomics):
+ *   gx[n] = d(gout[n] ssim[n]) / d x[n]  [N,H,W,C]; count[n] == 0: an all-zero gradient.  gx is neither x nor y.
+ * Every output is bit-reproducible and an image's results do not depend on the rest of the batch.
+ * 11 <= H, W <= 16384, 1 <= C <= 4, N >= 0, N * ceil(W/32) * ceil(H/16) <= 2^31 - 1, else MVIP_EINVAL before anything is
+ * touched; N == 0: MVIP_OK, nothing launched; with N > 0 a NULL operand other than mask / map / stash is MVIP_EINVAL. */
+int64_t mvip_ssim_tiles(int H, int W);
+int mvip_ssim_forward(const float *x, const float *y, const void *mask, int64_t N, int H, int W, int C, float *map,
+                      float *stash, double *partials, int *partial_counts, float *ssim, int *count, void *stream);
+int mvip_ssim_backward(const float *x, const float *y, const float *stash, const float *gout, const int *count, int64_t N,
+                       int H, int W, int C, float *gx, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -186,6 +186,9 @@ _SIGNATURES = {
     'mvip_harmonic_finish': (_int, [_i64, _int, _int, _c_f, _c_f, _c_f, _i64, _flt, _c_f]),
     'mvip_mask_dilate2d': (_int, [_c_f, _i64, _int, _int, _c_f, _c_f]),
     'mvip_warp_views': (_int, [_c_f, _c_f, _c_f, _i64, _int, _int, _c_f, _c_f, _c_f, _int, _c_f, _flt, _flt, _c_f, _c_f, _c_f, _c_f]),
+    'mvip_ssim_tiles': (_i64, [_int, _int]),
+    'mvip_ssim_forward': (_int, [_c_f, _c_f, _c_f, _i64, _int, _int, _int, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f]),
+    'mvip_ssim_backward': (_int, [_c_f, _c_f, _c_f, _c_f, _c_f, _i64, _int, _int, _int, _c_f, _c_f]),
 }
 
 # every symbol include/mvip_nerf.h declares; tests check the built library exports all of them

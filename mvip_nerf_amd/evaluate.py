@@ -1,0 +1,194 @@
+"""Evaluation of rendered views against targets (DS_NeRF/evaluation.py): PSNR, SSIM, L1 / L2, the depth L1 / L2 of its lines
+107-108, and the masked and bounding-box variants of the crop its lines 163-169 keep commented out.
+
+PSNR / L1 / L2 are the `img2mse` / `img2l1` / `mse2psnr` expressions in torch.  SSIM is ops.ssim (csrc/ssim.hip): an 11-tap Gaussian
+window on every channel, data range 1, no luminance conversion and no downsampling -- NOT pyiqa's Y-channel preprocessing, so
+figures are comparable within this project only.  LPIPS and FID need pretrained networks and are not computed.
+
+The host-only helpers (mask_bbox, pair_names, mean_of, write_report, read_report) need no GPU.
+"""
+import json
+import os
+
+import numpy as np
+import torch
+
+from .run_nerf_helpers import img2l1, img2mse, mse2psnr
+
+SSIM_MIN_SIDE = 11
+IMAGE_EXTENSIONS = ('png', 'jpg', 'jpeg', 'JPG')
+
+
+# ---- host-only helpers --------------------------------------------------------------------------------------------------------
+
+def mask_bbox(mask):
+    """(y0, y1, x0, x1), half-open, of the one rectangle around every set pixel of mask [H, W]; None for an empty mask."""
+    m = np.asarray(mask.detach().cpu() if torch.is_tensor(mask) else mask).astype(bool)
+    if m.ndim != 2:
+        raise ValueError(f'mask_bbox: mask [H, W] expected, got {m.shape}')
+    rows, cols = np.flatnonzero(m.any(1)), np.flatnonzero(m.any(0))
+    if rows.size == 0:
+        return None
+    return int(rows[0]), int(rows[-1]) + 1, int(cols[0]), int(cols[-1]) + 1
+
+
+def pair_names(pred_names, gt_names, what=('predictions', 'targets')):
+    """Pair two lists of file names by stem (the name without its extension), in sorted order: [(stem, pred, gt)].  A stem
+    without a partner, or one that occurs twice in a list, is an error.  (The reference pairs by os.listdir order, which is
+    unspecified.)"""
+    def by_stem(names, side):
+        out = {}
+        for n in names:
+            stem = os.path.splitext(os.path.basename(n))[0]
+            if stem in out:
+                raise ValueError(f'pair_names: {side}: {out[stem]} and {n} share the name {stem}')
+            out[stem] = n
+        return out
+    p, g = by_stem(pred_names, what[0]), by_stem(gt_names, what[1])
+    lone = sorted(set(p) - set(g)), sorted(set(g) - set(p))
+    if lone[0] or lone[1]:
+        raise ValueError(f'pair_names: without a partner: {what[0]} {lone[0]}, {what[1]} {lone[1]}')
+    return [(s, p[s], g[s]) for s in sorted(p)]
+
+
+def mean_of(values):
+    """Mean of the entries that are not None (None when there is none)."""
+    vals = [float(v) for v in values if v is not None]
+    return float(np.mean(vals)) if vals else None
+
+
+def summarise(per_view):
+    """{'per_view': {key: [..]}, 'mean': {key: mean over the views that have the value}, 'views': N}."""
+    n = len(next(iter(per_view.values()))) if per_view else 0
+    return {'views': n, 'per_view': per_view, 'mean': {k: mean_of(v) for k, v in per_view.items()}}
+
+
+def write_report(path, report):
+    """The report as JSON (indent 1); creates the directory.  Returns the path."""
+    d = os.path.dirname(os.path.abspath(path))
+    os.makedirs(d, exist_ok=True)
+    with open(path, 'w') as f:
+        json.dump(report, f, indent=1)
+        f.write('\n')
+    return path
+
+
+def read_report(path):
+    with open(path) as f:
+        return json.load(f)
+
+
+def _list_images(d):
+    return [f for f in sorted(os.listdir(d)) if f.rsplit('.', 1)[-1] in IMAGE_EXTENSIONS and '.' in f]
+
+
+# ---- metrics --------------------------------------------------------------------------------------------------------------------
+
+def _psnr(mse):
+    return float(mse2psnr(mse.reshape(1)))
+
+
+def image_metrics(pred, gt, mask=None):
+    """Per image: dict of lists (length N) psnr, ssim, l1, l2; with mask [N, H, W] bool also psnr_masked (over the masked
+    pixels; None for an empty mask), ssim_masked (ops.ssim(..., mask=mask): the map pixels centred on the mask), and psnr_bbox /
+    ssim_bbox on the crop to the one rectangle around the whole mask (None for an empty mask; ssim_bbox also None when the crop
+    is under 11 pixels in a dimension).  pred, gt [N, H, W, C] fp32 on the GPU in 0..1, C in 1..4; an image under 11 x 11 has
+    ssim None."""
+    from . import ops
+    if not (torch.is_tensor(pred) and torch.is_tensor(gt)) or pred.dim() != 4 or tuple(pred.shape) != tuple(gt.shape):
+        shape = lambda t: tuple(t.shape) if torch.is_tensor(t) else type(t).__name__
+        raise ValueError(f'image_metrics: pred {shape(pred)} and gt {shape(gt)}: two tensors [N, H, W, C] expected')
+    pred, gt = pred.detach().float().contiguous(), gt.detach().float().contiguous()
+    N, H, W, C = pred.shape
+    if mask is not None:
+        if not torch.is_tensor(mask) or mask.dtype != torch.bool or tuple(mask.shape) != (N, H, W):
+            raise ValueError(f'image_metrics: mask must be a bool tensor [{N}, {H}, {W}]')
+        mask = mask.detach().to(pred.device).contiguous()
+    big = H >= SSIM_MIN_SIDE and W >= SSIM_MIN_SIDE
+    out = {'psnr': [], 'ssim': ops.ssim(pred, gt).cpu().tolist() if big and N else [None] * N, 'l1': [], 'l2': []}
+    for n in range(N):
+        mse = img2mse(pred[n], gt[n])
+        out['psnr'].append(_psnr(mse))
+        out['l1'].append(float(img2l1(pred[n], gt[n])))
+        out['l2'].append(float(mse))
+    if mask is None:
+        return out
+    out['ssim_masked'] = ops.ssim(pred, gt, mask=mask).cpu().tolist() if big and N else [None] * N
+    out.update(psnr_masked=[], psnr_bbox=[], ssim_bbox=[])
+    host = mask.cpu().numpy()
+    for n in range(N):
+        box = mask_bbox(host[n])
+        if box is None:
+            for k in ('psnr_masked', 'psnr_bbox', 'ssim_bbox'):
+                out[k].append(None)
+            continue
+        out['psnr_masked'].append(_psnr(img2mse(pred[n][mask[n]], gt[n][mask[n]])))
+        y0, y1, x0, x1 = box
+        p, g = pred[n:n + 1, y0:y1, x0:x1].contiguous(), gt[n:n + 1, y0:y1, x0:x1].contiguous()
+        out['psnr_bbox'].append(_psnr(img2mse(p, g)))
+        out['ssim_bbox'].append(float(ops.ssim(p, g)) if min(y1 - y0, x1 - x0) >= SSIM_MIN_SIDE else None)
+    return out
+
+
+def evaluate_views(render_kwargs, hwf, poses, images, near, far, masks=None, disparities=None, chunk=1 << 15):
+    """Render every pose [N, 3, 4] without grad (run.render) and compare with images [N, H, W, 3] (image_metrics; masks
+    [N, H, W] bool adds the masked and bounding-box values).  With target disparities [N, H, W] the rendered disparity's
+    depth_l1 / depth_l2 are added (evaluation.py:107-108).  Returns summarise(...): per-view lists and their means."""
+    from . import run
+    H, W, focal = int(hwf[0]), int(hwf[1]), float(hwf[2])
+    poses = torch.as_tensor(poses)
+    if poses.dim() != 3 or tuple(poses.shape[1:]) != (3, 4):
+        raise ValueError(f'evaluate_views: poses [N, 3, 4] expected, got {tuple(poses.shape)}')
+    N = poses.shape[0]
+    images = torch.as_tensor(images)
+    if tuple(images.shape) != (N, H, W, 3):
+        raise ValueError(f'evaluate_views: images {tuple(images.shape)} for {N} views of {H} x {W}')
+    for name, t in (('masks', masks), ('disparities', disparities)):
+        if t is not None and tuple(t.shape) != (N, H, W):
+            raise ValueError(f'evaluate_views: {name} {tuple(t.shape)} for {N} views of {H} x {W}')
+    kw = dict(render_kwargs, near=near, far=far)
+    per_view = {}
+    with torch.no_grad():
+        for n in range(N):
+            rgb, disp = run.render(H, W, focal, chunk=int(chunk), c2w=poses[n], **kw)[:2]
+            dev = rgb.device
+            m = None if masks is None else torch.as_tensor(masks[n:n + 1]).to(dev).bool()
+            vals = image_metrics(rgb.reshape(1, H, W, 3), images[n:n + 1].to(dev).float(), m)
+            if disparities is not None:
+                target = torch.as_tensor(disparities[n]).to(dev).float()
+                vals['depth_l1'], vals['depth_l2'] = [float(img2l1(disp, target))], [float(img2mse(disp, target))]
+            for k, v in vals.items():
+                per_view.setdefault(k, []).extend(v)
+    return summarise(per_view)
+
+
+def evaluate_folders(pred_dir, gt_dir, mask_dir=None, device=None):
+    """The metrics of the images of pred_dir against those of gt_dir (8-bit, read with load_llff._imread, / 255), paired by
+    sorted name (pair_names: a name without a partner is an error); mask_dir: one mask per pair (non-zero = masked).  Returns
+    summarise(...) with the names added."""
+    from .load_llff import _imread
+    device = torch.device('cuda', torch.cuda.current_device()) if device is None else device
+    pairs = pair_names(_list_images(pred_dir), _list_images(gt_dir))
+    mask_of = None
+    if mask_dir is not None:
+        mask_of = {s: m for s, _, m in pair_names([p for _, p, _ in pairs], _list_images(mask_dir), what=('images', 'masks'))}
+    per_view = {}
+    load = lambda d, f: torch.from_numpy(np.ascontiguousarray(_imread(os.path.join(d, f))[..., :3]).astype(np.float32) / np.float32(255.))
+    for stem, p, g in pairs:
+        pred, gt = load(pred_dir, p), load(gt_dir, g)
+        if tuple(pred.shape) != tuple(gt.shape):
+            raise ValueError(f'evaluate_folders: {p} is {tuple(pred.shape)}, {g} is {tuple(gt.shape)}')
+        m = None
+        if mask_of is not None:
+            raw = np.asarray(_imread(os.path.join(mask_dir, mask_of[stem])))
+            raw = raw.reshape(raw.shape[0], raw.shape[1], -1).max(-1)
+            if raw.shape != tuple(pred.shape[:2]):
+                raise ValueError(f'evaluate_folders: mask {mask_of[stem]} is {raw.shape}, {p} is {tuple(pred.shape[:2])}')
+            m = torch.from_numpy(raw != 0)[None].to(device)
+        vals = image_metrics(pred[None].to(device), gt[None].to(device), m)
+        for k, v in vals.items():
+            per_view.setdefault(k, []).extend(v)
+    out = summarise(per_view)
+    out['names'] = [s for s, _, _ in pairs]
+    out['views'] = len(pairs)
+    return out

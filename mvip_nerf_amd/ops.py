@@ -2127,3 +2127,93 @@ def warp_views(tgt_disp, tgt_pose, tgt_mask, src_rgb, src_disp, src_pose, focal,
     call('mvip_warp_views', ptr(d), ptr(tp), ptr(m, torch.bool), N, H, W, ptr(sc), ptr(sd), ptr(sp), S, ptr(order.detach(), _I32),
          focal, tol, ptr(rgb), ptr(index, _I32), ptr(resid), stream())
     return rgb, index, resid
+
+
+# structural similarity with its gradient (beyond the reference, whose evaluation.py takes its metrics from pyiqa; csrc/ssim.hip) --
+
+SSIM_WINDOW = 11                 # taps; the map is [N, H - 10, W - 10, C]
+SSIM_TILE = (16, 32)             # map rows x columns per workgroup (csrc/ssim.hip: TY, TX)
+
+
+class _Ssim(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, y, mask, want_map):
+        N, H, W, C = x.shape
+        MH, MW = H - SSIM_WINDOW + 1, W - SSIM_WINDOW + 1
+        dev = x.device
+        need = ctx.needs_input_grad[0]
+        tiles = _lib.load().mvip_ssim_tiles(H, W)
+        if tiles < 0:
+            raise _lib.MvipError(f'ssim: images of {H} x {W} are beyond the kernels\' index range')
+        ssim = torch.empty((N,), device=dev, dtype=_F32)
+        count = torch.empty((N,), device=dev, dtype=_I32)
+        part = torch.empty((N * tiles,), device=dev, dtype=torch.float64)
+        pcnt = torch.empty((N * tiles,), device=dev, dtype=_I32)
+        smap = torch.empty((N, MH, MW, C), device=dev, dtype=_F32) if want_map else None
+        stash = torch.empty((3, N, MH, MW, C), device=dev, dtype=_F32) if need else None
+        call('mvip_ssim_forward', ptr(x), ptr(y), ptr(mask, torch.bool), N, H, W, C, ptr(smap), ptr(stash),
+             ptr(part, torch.float64), ptr(pcnt, _I32), ptr(ssim), ptr(count, _I32), stream())
+        if need:
+            ctx.save_for_backward(x, y, stash, count)
+        if smap is None:
+            ctx.mark_non_differentiable(count)
+            return ssim, count
+        ctx.mark_non_differentiable(count, smap)
+        return ssim, count, smap
+
+    @staticmethod
+    def backward(ctx, g_ssim, *_):
+        x, y, stash, count = ctx.saved_tensors
+        N, H, W, C = x.shape
+        gx = torch.empty_like(x)
+        call('mvip_ssim_backward', ptr(x), ptr(y), ptr(stash), ptr(_f32c(g_ssim)), ptr(count, _I32), N, H, W, C, ptr(gx), stream())
+        return gx, None, None, None
+
+
+def ssim(x, y, mask=None, return_map=False, return_count=False):
+    """Structural similarity of x against y, per image: ssim [N] fp32, or (ssim, map [N, H-10, W-10, C]) with return_map (and
+    count [N] int32, the counted map pixels, last with return_count).  x, y [N, H, W, C] fp32 on the GPU, contiguous,
+    channel-last (what run.render and the scene hold), C in 1..4, H, W >= 11; values in 0..1 (data range 1).  The definition is
+    csrc/ssim.hip's and tests/ssim_numpy.py's: an 11-tap Gaussian window (sigma 1.5) of "valid" extent, biased moments, C1 = 1e-4,
+    C2 = 9e-4, every channel on its own, mean over pixels and channels.  There is no luminance conversion and no downsampling:
+    this is NOT pyiqa's Y-channel preprocessing, and figures differ from it.  mask [N, H, W] bool: a map pixel counts iff the
+    mask is set at its centre (image pixel (i+5, j+5)); an image with no counted pixel gives exactly 1.0 and a zero gradient.
+    Gradient goes to x only (y and mask are detached); when x does not require grad nothing is stashed and the result has no
+    grad_fn.  Bit-reproducible, and an image's result does not depend on the rest of the batch."""
+    what = 'ssim'
+    for name, t in (('x', x), ('y', y)):
+        if not torch.is_tensor(t):
+            raise ValueError(f'{what}: {name} must be a tensor on the GPU, got {type(t).__name__}')
+        if t.dtype != _F32:
+            raise ValueError(f'{what}: {name} must be {_F32}, got {t.dtype}')
+        if t.dim() != 4:
+            raise ValueError(f'{what}: {name} must be [N, H, W, C], got {tuple(t.shape)}')
+    if tuple(x.shape) != tuple(y.shape):
+        raise ValueError(f'{what}: x {tuple(x.shape)} and y {tuple(y.shape)}: one shape expected')
+    N, H, W, C = x.shape
+    if not 1 <= C <= 4:
+        raise ValueError(f'{what}: 1 to 4 channels in the last dimension expected, got {tuple(x.shape)}')
+    if H < SSIM_WINDOW or W < SSIM_WINDOW:
+        raise ValueError(f'{what}: images of at least {SSIM_WINDOW} x {SSIM_WINDOW} expected, got {H} x {W}')
+    tensors = [x, y]
+    if mask is not None:
+        if not torch.is_tensor(mask) or mask.dtype != torch.bool or tuple(mask.shape) != (N, H, W):
+            got = f'{tuple(mask.shape)} {mask.dtype}' if torch.is_tensor(mask) else type(mask).__name__
+            raise ValueError(f'{what}: mask must be a {torch.bool} tensor [{N}, {H}, {W}] on the GPU, got {got}')
+        mask = mask.detach()
+        tensors.append(mask)
+    if not all(t.is_contiguous() for t in tensors):
+        raise ValueError(f'{what}: every operand must be contiguous')
+    _on_gpu(what, *tensors)
+    if any(t.device != x.device for t in tensors):
+        raise ValueError(f'{what}: tensors on one device expected, got {sorted({str(t.device) for t in tensors})}')
+    if N == 0:
+        out = (torch.empty((0,), device=x.device, dtype=_F32),)
+        if return_map:
+            out += (torch.empty((0, H - SSIM_WINDOW + 1, W - SSIM_WINDOW + 1, C), device=x.device, dtype=_F32),)
+        if return_count:
+            out += (torch.empty((0,), device=x.device, dtype=_I32),)
+        return out[0] if len(out) == 1 else out
+    res = _Ssim.apply(x, y.detach(), mask, bool(return_map))
+    out = (res[0],) + ((res[2],) if return_map else ()) + ((res[1].detach(),) if return_count else ())
+    return out[0] if len(out) == 1 else out

@@ -89,6 +89,7 @@ class SecondStageTrainer:
         self.N_rand = args.N_rand
         self.last_distortion = None                    # the step's distortion term (detached scalar), None when off
         self.last_reference = None                     # the step's reference term (detached scalar), None when off
+        self.last_reference_ssim = None                # the step's D-SSIM reference term (detached scalar), None when off
         # one flat bucket, reduced as two asynchronous halves [coarse network | fine network] (dist_utils.OverlappedGradBuckets);
         # MVIP_OVERLAP_ALLREDUCE=0 restores the single blocking all_reduce after the backward (A/B switch, same values)
         n_coarse = len(list(self.kw_train['network_fn'].parameters())) if self.kw_train.get('network_fn') is not None else 0
@@ -312,6 +313,25 @@ class SecondStageTrainer:
             if ref is not None:
                 self.last_reference = (ref_lambda * ref).detach()
                 loss = loss + ref_lambda * ref
+        # D-SSIM reference term (extension, default off: args.reference_ssim_lambda absent or 0 leaves the step as it is): the L2 of
+        # the reference term pulls toward the blur of warped and harmonically filled references; lambda * mean_n(1 - SSIM) on the
+        # assembled frame `combin` (which already carries the masked render's autograd history) against the scene's image,
+        # counted where the view's mask (and scene.reference_valid, where that exists) is set at the window's centre.  With
+        # world > 1 every rank evaluates the same frame and the gradient reaches its own shard only, as for a replicated SDS term.
+        self.last_reference_ssim = None
+        ssim_lambda = float(getattr(args, 'reference_ssim_lambda', 0.) or 0.)
+        if ssim_lambda > 0 and self.guidance is not None:
+            if sc.H < ops.SSIM_WINDOW or sc.W < ops.SSIM_WINDOW:
+                raise ValueError(f'reference_ssim_lambda: the frame is {sc.H} x {sc.W}; SSIM needs at least {ops.SSIM_WINDOW} x '
+                                 f'{ops.SSIM_WINDOW} (its window)')
+            m_ssim = sc.mask_of(img_i).reshape(1, sc.H, sc.W).bool()
+            valid = getattr(sc, 'reference_valid', None)
+            if valid is not None:
+                m_ssim = m_ssim & valid[img_i].reshape(1, sc.H, sc.W)
+            target = sc.images[img_i].detach().reshape(1, sc.H, sc.W, 3).float().contiguous()
+            dssim = (1.0 - ops.ssim(combin.reshape(1, sc.H, sc.W, 3).contiguous(), target, mask=m_ssim.contiguous())).mean()
+            self.last_reference_ssim = (ssim_lambda * dssim).detach()
+            loss = loss + ssim_lambda * dssim
         # ray distortion loss of the two supervision renders (mip-NeRF 360 eq. 15; the masked SDS render and the neighbour views
         # are not regularised), shard means weighted like the terms above, empty shards skipped
         self.last_distortion = None
