@@ -18,6 +18,12 @@ static inline int check_launch() {
 
 static inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
+// false for NaN and +-inf (a comparison, on the host and on the device alike)
+__host__ __device__ __forceinline__ bool finite(float x) { return fabsf(x) <= 3.402823466e38f; }
+
+// workgroups of `per` items that cover n
+static inline unsigned blocks_for(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
+
 // Zeroing of small scratch words as a KERNEL, not hipMemsetAsync: inside a captured hipGraph the 16-byte memset
 // node in front of an atomicMax reduction was seen to leave stale values on replay (the conv data-gradient scale of
 // the graphed SDS step drifted from replay to replay); a kernel node is ordered like every other launch.

@@ -103,7 +103,7 @@ __global__ __launch_bounds__(BLOCK) void mark_kernel(const float *__restrict__ v
             if (y >= s.H) break;
             const long long p = n * s.HW + (long long)y * s.W + x;
             const float val = v[p];
-            const bool u = m[p] != 0 || !(fabsf(val) <= 3.402823466e38f);
+            const bool u = m[p] != 0 || !finite(val);
             w.um[p] = u ? 1 : 0;
             out[p] = val;
             c += u;

@@ -1,16 +1,14 @@
 // Indexed, crack-free marching cubes over a dense fp32 grid (beyond the reference: MVIP-NeRF has no mesh export).
 //
 // grid [nx, ny, nz], C-contiguous, z fastest; point (i, j, k) sits at bmin + (i, j, k) * (bmax - bmin) / (n - 1).
-// Every pass partitions the points the same way: workgroup b owns the PPB = 1024 consecutive linear indices starting at
-// b * PPB, thread t of it the indices b * PPB + q * 256 + t, q = 0..3 (coalesced).  Within a workgroup each count
-// is scanned in linear-index order on the wave's ballot masks (v_mbcnt per bit plane of the 0..3 / 0..5 counts) plus four
-// wave totals in LDS, so the output order is fixed by the scans and the result is reproducible bit for bit.
+// Every pass partitions the points, and ranks the 0..3 vertices / 0..5 triangles of each, as csrc/compact_device.h says: the
+// output order is fixed by the scans and the result is reproducible bit for bit.
 //
 //   1. mc_classify:  per point the crossing flags of its three owned lattice edges (+x, +y, +z: 0..3 vertices) and, for a
 //      cell origin, the 8-bit cube index; one uint16 per point = cube | flags << 8.  Workgroup totals of vertices and
 //      triangles (the triangle count of each cube index, read off the table, staged in LDS); a non-finite value raises a
 //      device flag with a plain vector store.
-//   2. mc_scan:      one workgroup: exclusive int64 scan of the workgroup totals in place, and the two grand totals.
+//   2. scan:         one workgroup: exclusive int64 scan of the workgroup totals in place, and the two grand totals.
 //      The host reads the totals once, to allocate the outputs (the only synchronisation).
 //   3. mc_vertices:  per point its first vertex id (int32), and per crossing edge the position and the normal: the
 //      central-difference gradient of sigma at both endpoints (one-sided on the grid's faces), interpolated with the
@@ -23,54 +21,14 @@
 // Conventions (shared with tests/mc_numpy.py): corner c = dx + 2 dy + 4 dz; edge e = 4 * axis + r; a corner is inside iff
 // v >= iso; t = (iso - v0) / (v1 - v0), p = p0 + t (p1 - p0); vertices ordered by (point, axis), triangles by (cell,
 // table slot); the triangle table (mvip_nerf_amd/mesh.py, 256 x 16 int8, -1 terminated) is passed in device memory.
-#include "common.h"
+#include "bitgrid_device.h"
+#include "compact_device.h"
 
 namespace mvip {
 namespace mc {
 
-constexpr int BLOCK = 256;
-constexpr int PPT = 4;                       // points per thread
-constexpr int PPB = BLOCK * PPT;             // points per workgroup
-constexpr int SCAN_BLOCK = 1024;
-constexpr int SCAN_PER_THREAD = 8;
-
-__device__ __forceinline__ int lanes_below(unsigned long long m) {
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-}
-
-// exclusive prefix across the wave of a count in 0..7, from its three bit planes; `total` = the wave's sum
-__device__ __forceinline__ int wave_excl_small(int c, int &total) {
-    int pre = 0;
-    total = 0;
-#pragma unroll
-    for (int b = 0; b < 3; ++b) {
-        const unsigned long long m = __ballot((c >> b) & 1);
-        pre += lanes_below(m) << b;
-        total += __popcll(m) << b;
-    }
-    return pre;
-}
-
-// exclusive prefix across the workgroup (4 waves, lane order = linear order); `total` = the workgroup's sum.
-// wtot: 4 LDS words of this call's buffer (callers alternate two buffers, so one barrier per call suffices).
-__device__ __forceinline__ int block_excl_small(int c, int *wtot, int &total) {
-    const int w = threadIdx.x >> 6;
-    int wt;
-    const int pre = wave_excl_small(c, wt);
-    if ((threadIdx.x & 63) == 0) wtot[w] = wt;
-    __syncthreads();
-    const int t0 = wtot[0], t1 = wtot[1], t2 = wtot[2], t3 = wtot[3];
-    total = t0 + t1 + t2 + t3;
-    return pre + (w > 0 ? t0 : 0) + (w > 1 ? t1 : 0) + (w > 2 ? t2 : 0);
-}
-
-__device__ __forceinline__ void point_ijk(int n, int ny, int nz, int &i, int &j, int &k) {
-    const int sx = ny * nz;
-    i = n / sx;
-    const int r = n - i * sx;
-    j = r / nz;
-    k = r - j * nz;
-}
+using namespace compact;
+using bitgrid::linear_ijk;
 
 __device__ __forceinline__ int tri_count(const signed char *tab, int cube) {
     int c = 0;
@@ -95,9 +53,9 @@ __global__ __launch_bounds__(BLOCK) void mc_classify_kernel(const float *__restr
         int nv = 0, nt = 0;
         if (n < N) {
             int i, j, k;
-            point_ijk(n, ny, nz, i, j, k);
+            linear_ijk(n, ny, nz, i, j, k);
             const float v0 = v[n];
-            if (!(fabsf(v0) <= 3.402823466e38f)) *nonfinite = 1u;      // NaN or +-inf
+            if (!finite(v0)) *nonfinite = 1u;      // NaN or +-inf
             const bool xi = i + 1 < nx, yi = j + 1 < ny, zi = k + 1 < nz;
             const unsigned c0 = v0 >= iso;
             const unsigned c1 = xi ? (v[n + sx] >= iso) : c0;
@@ -115,8 +73,8 @@ __global__ __launch_bounds__(BLOCK) void mc_classify_kernel(const float *__restr
             nt = counts[cube];
         }
         int wv, wt;
-        wave_excl_small(nv, wv);
-        wave_excl_small(nt, wt);
+        wave_excl_small<3>(nv, wv);
+        wave_excl_small<3>(nt, wt);
         vsum += wv;
         tsum += wt;
     }
@@ -127,55 +85,6 @@ __global__ __launch_bounds__(BLOCK) void mc_classify_kernel(const float *__restr
         wg_sums[2 * (long long)blockIdx.x] = (long long)wtot[0][0] + wtot[0][1] + wtot[0][2] + wtot[0][3];
         wg_sums[2 * (long long)blockIdx.x + 1] = (long long)wtot[1][0] + wtot[1][1] + wtot[1][2] + wtot[1][3];
     }
-}
-
-__device__ __forceinline__ long long wave_incl_i64(long long x) {
-    const int l = threadIdx.x & 63;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const long long y = __shfl_up(x, o, 64);
-        if (l >= o) x += y;
-    }
-    return x;
-}
-
-// in-place exclusive scan of G (vertex, triangle) pairs; totals[0..1] = the sums.  One workgroup of 1024 threads, each
-// thread owning SCAN_PER_THREAD consecutive pairs of a 8192-pair chunk.
-__global__ __launch_bounds__(SCAN_BLOCK) void mc_scan_kernel(long long *__restrict__ wg, long long G,
-                                                             long long *__restrict__ totals) {
-    __shared__ long long wsum[2][SCAN_BLOCK / 64][2];
-    long long carry_v = 0, carry_t = 0;
-    const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-    int buf = 0;
-    for (long long c0 = 0; c0 < G; c0 += (long long)SCAN_BLOCK * SCAN_PER_THREAD) {
-        const long long g0 = c0 + (long long)threadIdx.x * SCAN_PER_THREAD;
-        long long sv = 0, st = 0;
-        for (int e = 0; e < SCAN_PER_THREAD; ++e)
-            if (g0 + e < G) { sv += wg[2 * (g0 + e)]; st += wg[2 * (g0 + e) + 1]; }
-        const long long iv = wave_incl_i64(sv), it = wave_incl_i64(st);
-        if (l == 63) { wsum[buf][w][0] = iv; wsum[buf][w][1] = it; }
-        __syncthreads();
-        long long bv = 0, bt = 0, tv = 0, tt = 0;
-        for (int u = 0; u < SCAN_BLOCK / 64; ++u) {
-            const long long a = wsum[buf][u][0], b = wsum[buf][u][1];
-            if (u < w) { bv += a; bt += b; }
-            tv += a;
-            tt += b;
-        }
-        long long ev = carry_v + bv + iv - sv, et = carry_t + bt + it - st;
-        for (int e = 0; e < SCAN_PER_THREAD; ++e)
-            if (g0 + e < G) {
-                const long long a = wg[2 * (g0 + e)], b = wg[2 * (g0 + e) + 1];
-                wg[2 * (g0 + e)] = ev;
-                wg[2 * (g0 + e) + 1] = et;
-                ev += a;
-                et += b;
-            }
-        carry_v += tv;
-        carry_t += tt;
-        buf ^= 1;
-    }
-    if (threadIdx.x == 0) { totals[0] = carry_v; totals[1] = carry_t; }
 }
 
 // d sigma / d axis at point n (index ii of nn along the axis, stride s, spacing h): central inside, one-sided on a face
@@ -198,13 +107,13 @@ __global__ __launch_bounds__(BLOCK) void mc_vertices_kernel(const float *__restr
         const int n = blockIdx.x * PPB + q * BLOCK + threadIdx.x;
         const unsigned mask = n < N ? (unsigned)(flags[n] >> 8) : 0u;
         int total;
-        const int pre = block_excl_small(__popc(mask), wtot[q & 1], total);
+        const int pre = block_excl_small<3>(__popc(mask), wtot[q & 1], total);
         if (n < N) {
             long long id = base + pre;
             vid[n] = (int)id;
             if (mask) {
                 int i, j, k;
-                point_ijk(n, ny, nz, i, j, k);
+                linear_ijk(n, ny, nz, i, j, k);
                 const float v0 = v[n];
                 const float px = x0 + (float)i * hx, py = y0 + (float)j * hy, pz = z0 + (float)k * hz;
                 const float g0x = grad1(v, n, i, nx, sx, hx), g0y = grad1(v, n, j, ny, sy, hy), g0z = grad1(v, n, k, nz, 1, hz);
@@ -254,7 +163,7 @@ __global__ __launch_bounds__(BLOCK) void mc_triangles_kernel(int nx, int ny, int
         const int cube = n < N ? (int)(flags[n] & 0xffu) : 0;
         const int nt = tri_count(tab, cube);
         int total;
-        const int pre = block_excl_small(nt, wtot[q & 1], total);
+        const int pre = block_excl_small<3>(nt, wtot[q & 1], total);
         for (int s = 0; s < nt; ++s) {
             const long long f = base + pre + s;
 #pragma unroll
@@ -279,7 +188,6 @@ using namespace mvip;
 static inline bool mc_shape_ok(int nx, int ny, int nz) {
     return nx >= 2 && nx <= 768 && ny >= 2 && ny <= 768 && nz >= 2 && nz <= 768;
 }
-static inline bool mc_finite(float x) { return fabsf(x) <= 3.402823466e38f; }
 
 extern "C" int64_t mvip_mcubes_groups(int nx, int ny, int nz) {
     if (!mc_shape_ok(nx, ny, nz)) return -1;
@@ -288,15 +196,15 @@ extern "C" int64_t mvip_mcubes_groups(int nx, int ny, int nz) {
 
 extern "C" int mvip_mcubes_count(const float *grid, int nx, int ny, int nz, float iso, const void *tri_table, void *flags,
                                  int64_t *wg, int64_t *totals, void *stream) {
-    if (!mc_shape_ok(nx, ny, nz) || !(iso > 0.f) || !mc_finite(iso)) return MVIP_EINVAL;
+    if (!mc_shape_ok(nx, ny, nz) || !(iso > 0.f) || !finite(iso)) return MVIP_EINVAL;
     if (!grid || !tri_table || !flags || !wg || !totals) return MVIP_EINVAL;
     hipStream_t s = as_stream(stream);
     const int64_t G = mvip_mcubes_groups(nx, ny, nz);
     zero_words(totals + 2, 2, s);                               // totals[2]: the non-finite flag
     hipLaunchKernelGGL(mc::mc_classify_kernel, dim3((unsigned)G), dim3(mc::BLOCK), 0, s, grid, nx, ny, nz, iso,
                        (const signed char *)tri_table, (unsigned short *)flags, (long long *)wg, (unsigned *)(totals + 2));
-    hipLaunchKernelGGL(mc::mc_scan_kernel, dim3(1), dim3(mc::SCAN_BLOCK), 0, s, (long long *)wg, (long long)G,
-                       (long long *)totals);
+    hipLaunchKernelGGL((compact::scan_kernel<long long, 2>), dim3(1), dim3(compact::SCAN_BLOCK), 0, s, (long long *)wg,
+                       (int)G, (long long *)totals);
     return check_launch();
 }
 
@@ -304,8 +212,8 @@ extern "C" int mvip_mcubes_emit(const float *grid, int nx, int ny, int nz, float
                                 float y1, float z1, const void *tri_table, const void *flags, const int64_t *wg,
                                 int64_t n_verts, int64_t n_tris, int *vid, float *verts, float *normals, int *faces,
                                 void *stream) {
-    if (!mc_shape_ok(nx, ny, nz) || !(iso > 0.f) || !mc_finite(iso)) return MVIP_EINVAL;
-    if (!mc_finite(x0) || !mc_finite(y0) || !mc_finite(z0) || !mc_finite(x1) || !mc_finite(y1) || !mc_finite(z1) ||
+    if (!mc_shape_ok(nx, ny, nz) || !(iso > 0.f) || !finite(iso)) return MVIP_EINVAL;
+    if (!finite(x0) || !finite(y0) || !finite(z0) || !finite(x1) || !finite(y1) || !finite(z1) ||
         !(x0 < x1) || !(y0 < y1) || !(z0 < z1)) return MVIP_EINVAL;
     if (n_verts < 0 || n_tris < 0 || n_verts > 3 * (int64_t)nx * ny * nz || n_tris > (int64_t)INT32_MAX) return MVIP_EINVAL;
     if (n_verts == 0 && n_tris == 0) return MVIP_OK;

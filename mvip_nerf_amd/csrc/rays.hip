@@ -259,7 +259,6 @@ __global__ void __launch_bounds__(256) posenc_tile_kernel(const float *__restric
     for (int64_t i = (c4 << 2) + threadIdx.x; i < cnt; i += 256) dst[i] = tile[i];
 }
 
-static inline unsigned blocks_for(int64_t n, int t) { return (unsigned)((n + t - 1) / t); }
 
 }  // namespace mvip
 

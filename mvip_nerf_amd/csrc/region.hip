@@ -1,16 +1,12 @@
 // Regions: "the surfaces to be inpainted" as a set of cells of a box, lifted from annotated 2D masks and rendered into any
 // view (beyond the reference, which takes its masks as given; mvip_nerf_amd/region.py).
 //
-// The bit grid is occupancy's (csrc/occupancy.hip): box [bmin, bmax] cut into (cx, cy, cz) cells, cell of a point p per axis
-// in fp32 f = floorf((p - bmin) * inv), inv = cells / (bmax - bmin) rounded once on the host; p is in the box iff
-// 0 <= f < c on all three axes (a NaN or infinite coordinate fails the comparison: outside).  Linear cell
-// l = (ix * cy + iy) * cz + iz (z fastest), bit l & 31 of 32-bit word l >> 5, unused tail bits zero.
-// The one difference, and the reason for kernels of their own: inside(p) = in the box AND bit set (occupancy's keep(p) is
-// "outside the box OR bit set").  (Conventions shared with mvip_nerf_amd/region.py and tests/region_numpy.py.)
+// The grid is the bit grid of csrc/bitgrid_device.h, the one occupancy uses.  The one difference, and the reason for kernels
+// of their own: inside(p) = in the box AND bit set (occupancy's keep(p) is "outside the box OR bit set").
 //
 //   region_mark:       points [P, 3] -> bits: every point in the box ORs its bit into `words` (in / out: bits already set stay
 //                      set).  One thread per point, one vector atomicOr on the word, skipped when a plain load already shows
-//                      the bit (bits are only ever set, so a set bit seen is a set bit).  csrc/occupancy.hip advertises "no
+//                      the bit (bits are only ever set, so a set bit seen is a set bit).  csrc/compact_device.h advertises "no
 //                      atomics"; this pass is deterministic for a different reason: OR is commutative and idempotent, so the
 //                      words do not depend on the order of execution and the result is reproducible bit for bit.
 //   region_accumulate: out[b] = sum over j of (inside(p_bj) ? weights[b, j] : 0), p_bj = rows[b, 0:3] + rows[b, 3:6] * z[b, j]
@@ -25,7 +21,7 @@
 //                      the loads of four rays are in flight together (one ray per wave: 56 us per 378 x 504 x 128 frame, four:
 //                      44 us; a wave that moves 1 KB lives for little but its three dependent round trips).  No LDS, no scratch.
 //   region_lookup:     inside(p) of a list of points.
-#include "common.h"
+#include "bitgrid_device.h"
 
 namespace mvip {
 namespace region {
@@ -34,21 +30,11 @@ constexpr int BLOCK = 256;
 constexpr int RAYS_PER_WAVE = 4;             // accumulate: consecutive rays per wave, their loads in flight together
 constexpr int RAYS_PER_BLOCK = BLOCK / MVIP_WAVE * RAYS_PER_WAVE;
 
-struct Grid {
-    float bx, by, bz, ix, iy, iz;
-    int cx, cy, cz;
-};
-
-// linear cell of a point, -1 outside the box
-__device__ __forceinline__ int cell_of(const Grid &g, float x, float y, float z) {
-    const float fx = floorf((x - g.bx) * g.ix), fy = floorf((y - g.by) * g.iy), fz = floorf((z - g.bz) * g.iz);
-    const bool in_box = fx >= 0.f && fx < (float)g.cx && fy >= 0.f && fy < (float)g.cy && fz >= 0.f && fz < (float)g.cz;
-    return in_box ? ((int)fx * g.cy + (int)fy) * g.cz + (int)fz : -1;
-}
+using namespace bitgrid;
 
 __device__ __forceinline__ bool inside(const Grid &g, const unsigned *__restrict__ words, float x, float y, float z) {
     const int l = cell_of(g, x, y, z);
-    return l >= 0 && ((words[l >> 5] >> (l & 31)) & 1u);
+    return l >= 0 && cell_bit(words, l);
 }
 
 __global__ __launch_bounds__(BLOCK) void region_mark_kernel(const float *__restrict__ pts, long long P, const Grid g,
@@ -104,48 +90,36 @@ __global__ __launch_bounds__(BLOCK) void region_lookup_kernel(const float *__res
 
 using namespace mvip;
 
-static inline bool region_finite(float x) { return fabsf(x) <= 3.402823466e38f; }
-static inline bool region_grid(const float *box, const int *cells, const int *words, region::Grid &g) {
-    if (!box || !cells || !words) return false;
-    for (int a = 0; a < 3; ++a)
-        if (cells[a] < 1 || cells[a] > 512) return false;
-    for (int a = 0; a < 6; ++a)
-        if (!region_finite(box[a])) return false;
-    if (!(box[3] > 0.f) || !(box[4] > 0.f) || !(box[5] > 0.f)) return false;
-    g = region::Grid{box[0], box[1], box[2], box[3], box[4], box[5], cells[0], cells[1], cells[2]};
-    return true;
-}
-static inline unsigned region_blocks(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 constexpr int64_t REGION_MAX_POINTS = (int64_t)INT32_MAX * (int64_t)region::BLOCK;
 
 extern "C" int mvip_region_mark(const float *pts, int64_t P, const float *box, const int *cells, int *words, void *stream) {
-    region::Grid g;
-    if (P < 0 || P > REGION_MAX_POINTS || !region_grid(box, cells, words, g)) return MVIP_EINVAL;
+    bitgrid::Grid g;
+    if (P < 0 || P > REGION_MAX_POINTS || !bitgrid::grid_from_args(box, cells, words, g)) return MVIP_EINVAL;
     if (P == 0) return MVIP_OK;
     if (!pts) return MVIP_EINVAL;
-    hipLaunchKernelGGL(region::region_mark_kernel, dim3(region_blocks(P, region::BLOCK)), dim3(region::BLOCK), 0,
+    hipLaunchKernelGGL(region::region_mark_kernel, dim3(blocks_for(P, region::BLOCK)), dim3(region::BLOCK), 0,
                        as_stream(stream), pts, (long long)P, g, (unsigned *)words);
     return check_launch();
 }
 
 extern "C" int mvip_region_accumulate(const float *rows, const float *z, const float *weights, int64_t B, int S,
                                       const float *box, const int *cells, const int *words, float *out, void *stream) {
-    region::Grid g;
-    if (B < 0 || S < 1 || B > (int64_t)INT32_MAX / S || !region_grid(box, cells, words, g)) return MVIP_EINVAL;
+    bitgrid::Grid g;
+    if (B < 0 || S < 1 || B > (int64_t)INT32_MAX / S || !bitgrid::grid_from_args(box, cells, words, g)) return MVIP_EINVAL;
     if (B == 0) return MVIP_OK;
     if (!rows || !z || !weights || !out) return MVIP_EINVAL;
-    hipLaunchKernelGGL(region::region_accumulate_kernel, dim3(region_blocks(B, region::RAYS_PER_BLOCK)), dim3(region::BLOCK), 0,
+    hipLaunchKernelGGL(region::region_accumulate_kernel, dim3(blocks_for(B, region::RAYS_PER_BLOCK)), dim3(region::BLOCK), 0,
                        as_stream(stream), rows, z, weights, (long long)B, S, g, (const unsigned *)words, out);
     return check_launch();
 }
 
 extern "C" int mvip_region_lookup(const float *pts, int64_t P, const float *box, const int *cells, const int *words, void *out,
                                   void *stream) {
-    region::Grid g;
-    if (P < 0 || P > REGION_MAX_POINTS || !region_grid(box, cells, words, g)) return MVIP_EINVAL;
+    bitgrid::Grid g;
+    if (P < 0 || P > REGION_MAX_POINTS || !bitgrid::grid_from_args(box, cells, words, g)) return MVIP_EINVAL;
     if (P == 0) return MVIP_OK;
     if (!pts || !out) return MVIP_EINVAL;
-    hipLaunchKernelGGL(region::region_lookup_kernel, dim3(region_blocks(P, region::BLOCK)), dim3(region::BLOCK), 0,
+    hipLaunchKernelGGL(region::region_lookup_kernel, dim3(blocks_for(P, region::BLOCK)), dim3(region::BLOCK), 0,
                        as_stream(stream), pts, (long long)P, g, (const unsigned *)words, (unsigned char *)out);
     return check_launch();
 }

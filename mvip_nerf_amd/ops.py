@@ -1812,16 +1812,27 @@ def marching_cubes(grid, iso, bound_min, bound_max, tri_table):
 _I32 = torch.int32
 
 
-def _occ_args(box, cells):
-    """The grid's host-side arguments: box = (bmin[3], inv[3]) as six C floats, cells as three C ints."""
-    import ctypes
-    return (ctypes.c_float * 6)(*[float(v) for v in box]), (ctypes.c_int * 3)(*[int(c) for c in cells])
-
-
 def occupancy_words(cells):
     """Number of int32 words of a grid of `cells` = (cx, cy, cz): one bit per cell, z fastest."""
     cx, cy, cz = (int(c) for c in cells)
     return (cx * cy * cz + 31) // 32
+
+
+def _grid_args(who, box, cells, words, ok=True, shapes=''):
+    """The grid's host-side arguments, after the check that `words` fits `cells`: box = (bmin[3], inv[3]) as six C floats,
+    cells as three C ints.  ok / shapes: the caller's own shape check and its shapes, for the one message."""
+    import ctypes
+    if not ok or tuple(words.shape) != (occupancy_words(cells),):
+        raise _lib.MvipError(f'{who}: {shapes}{tuple(words.shape)} words for cells {tuple(cells)}')
+    return (ctypes.c_float * 6)(*[float(v) for v in box]), (ctypes.c_int * 3)(*[int(c) for c in cells])
+
+
+def _grid_lookup(who, pts, box, cells, words):
+    p = _f32c(pts.reshape(-1, 3))
+    cbox, ccells = _grid_args(who, box, cells, words)
+    out = torch.empty(p.shape[0], device=p.device, dtype=torch.uint8)
+    call('mvip_' + who, ptr(p), p.shape[0], cbox, ccells, ptr(words, _I32), ptr(out, torch.uint8), stream())
+    return out
 
 
 def occupancy_build(sigma, cells, samples_per_cell, threshold):
@@ -1854,10 +1865,8 @@ def occupancy_compact(rows, z, box, cells, words, want_mask=False, want_pts=Fals
     rows, z = _f32c(rows), _f32c(z)
     B, S = z.shape
     dev = z.device
-    if tuple(rows.shape) != (B, 11) or tuple(words.shape) != (occupancy_words(cells),):
-        raise _lib.MvipError(f'occupancy_compact: rows {tuple(rows.shape)}, z {tuple(z.shape)}, {tuple(words.shape)} words '
-                             f'for cells {tuple(cells)}')
-    cbox, ccells = _occ_args(box, cells)
+    cbox, ccells = _grid_args('occupancy_compact', box, cells, words, tuple(rows.shape) == (B, 11),
+                              f'rows {tuple(rows.shape)}, z {tuple(z.shape)}, ')
     G = _lib.load().mvip_occupancy_groups(B, S)
     if G < 0:
         raise _lib.MvipError(f'occupancy_compact: {B} x {S} samples exceed int32 sample indices')
@@ -1893,13 +1902,7 @@ def scatter_raw(raw_k, idx, shape):
 
 def occupancy_lookup(pts, box, cells, words):
     """keep(p) of pts [P, 3]: uint8 [P], 1 = outside the box or in an occupied cell."""
-    p = _f32c(pts.reshape(-1, 3))
-    if tuple(words.shape) != (occupancy_words(cells),):
-        raise _lib.MvipError(f'occupancy_lookup: {tuple(words.shape)} words for cells {tuple(cells)}')
-    out = torch.empty(p.shape[0], device=p.device, dtype=torch.uint8)
-    cbox, ccells = _occ_args(box, cells)
-    call('mvip_occupancy_lookup', ptr(p), p.shape[0], cbox, ccells, ptr(words, _I32), ptr(out, torch.uint8), stream())
-    return out
+    return _grid_lookup('occupancy_lookup', pts, box, cells, words)
 
 
 # regions: 3D-consistent inpainting masks (beyond the reference, mvip_nerf_amd/region.py, csrc/region.hip) -----------------
@@ -1908,9 +1911,7 @@ def occupancy_lookup(pts, box, cells, words):
 def region_mark(pts, box, cells, words):
     """OR the bit of every point of pts [P, 3] that lies in the box into `words` (in place; returns words)."""
     p = _f32c(pts.reshape(-1, 3))
-    if tuple(words.shape) != (occupancy_words(cells),):
-        raise _lib.MvipError(f'region_mark: {tuple(words.shape)} words for cells {tuple(cells)}')
-    cbox, ccells = _occ_args(box, cells)
+    cbox, ccells = _grid_args('region_mark', box, cells, words)
     call('mvip_region_mark', ptr(p), p.shape[0], cbox, ccells, ptr(words, _I32), stream())
     return words
 
@@ -1920,24 +1921,16 @@ def region_accumulate(rows, z, weights, box, cells, words):
     weights [B, S].  No autograd: the inputs are read as they are."""
     rows, z, weights = _f32c(rows.detach()), _f32c(z.detach()), _f32c(weights.detach())
     B, S = z.shape
-    if tuple(rows.shape) != (B, 11) or tuple(weights.shape) != (B, S) or tuple(words.shape) != (occupancy_words(cells),):
-        raise _lib.MvipError(f'region_accumulate: rows {tuple(rows.shape)}, z {tuple(z.shape)}, weights {tuple(weights.shape)}, '
-                             f'{tuple(words.shape)} words for cells {tuple(cells)}')
+    cbox, ccells = _grid_args('region_accumulate', box, cells, words, tuple(rows.shape) == (B, 11) and tuple(weights.shape) == (B, S),
+                              f'rows {tuple(rows.shape)}, z {tuple(z.shape)}, weights {tuple(weights.shape)}, ')
     out = torch.empty(B, device=z.device, dtype=_F32)
-    cbox, ccells = _occ_args(box, cells)
     call('mvip_region_accumulate', ptr(rows), ptr(z), ptr(weights), B, S, cbox, ccells, ptr(words, _I32), ptr(out), stream())
     return out
 
 
 def region_lookup(pts, box, cells, words):
     """inside(p) of pts [P, 3]: uint8 [P], 1 = in the box and in a cell of the region."""
-    p = _f32c(pts.reshape(-1, 3))
-    if tuple(words.shape) != (occupancy_words(cells),):
-        raise _lib.MvipError(f'region_lookup: {tuple(words.shape)} words for cells {tuple(cells)}')
-    out = torch.empty(p.shape[0], device=p.device, dtype=torch.uint8)
-    cbox, ccells = _occ_args(box, cells)
-    call('mvip_region_lookup', ptr(p), p.shape[0], cbox, ccells, ptr(words, _I32), ptr(out, torch.uint8), stream())
-    return out
+    return _grid_lookup('region_lookup', pts, box, cells, words)
 
 
 # ray distortion loss (mip-NeRF 360 eq. 15; beyond the reference, csrc/distortion.hip) ------------------------------------------

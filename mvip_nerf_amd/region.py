@@ -8,13 +8,10 @@ keyword -> 'region_map'; propagate_masks thresholds it).  A ray that is stopped 
 no weight inside it: the masks are occlusion-aware.  Region.carve() gives the occupancy grid that renders the scene with
 the region cut out -- the hole the inpainting has to fill.
 
-Conventions: exactly occupancy's (occupancy.py, csrc/occupancy.hip, tests/occupancy_numpy.py): box [bmin, bmax], cells =
-(cx, cy, cz) each 1..512, inv = cells / (bmax - bmin) formed in fp64 and rounded once to fp32, cell of a point per axis
-f = floorf((p - bmin) * inv), in the box iff 0 <= f < c on all axes (NaN / inf: outside), linear cell
-l = (ix * cy + iy) * cz + iz, bit l & 31 of int32 word l >> 5, unused tail bits zero.  A sample's point is
-row[0:3] + row[3:6] * z in the expression of the MLP ray kernels.  ONE difference, the reason for a type of its own:
-inside(p) = in the box AND bit set (occupancy's keep(p) is "outside the box OR bit set").  The kernels are
-csrc/region.hip; there is no CPU path.
+The grid is a bitgrid.BitGrid, the one occupancy uses (the box, the cells and the word layout: bitgrid.py).  A sample's
+point is row[0:3] + row[3:6] * z in the expression of the MLP ray kernels.  ONE difference, the reason for a type of its own:
+inside(p) = in the box AND bit set (occupancy's keep(p) is "outside the box OR bit set").  The kernels are csrc/region.hip;
+there is no CPU path.
 
 Choosing the grid (from a CPU simulation of a ball in front of a wall, 64 + 64 samples): keep the cell edge above the
 pixel footprint at the object's depth -- at 0.78 x the footprint the marked shell has holes and mask errors reach 4 cells,
@@ -25,7 +22,8 @@ import numpy as np
 import torch
 
 from . import mesh, ops
-from .occupancy import FORMAT_VERSION, MAX_CELLS_PER_AXIS, OccupancyGrid, _cells, _count, cell_inverse
+from .bitgrid import MAX_CELLS_PER_AXIS, BitGrid, _cells, _count
+from .occupancy import OccupancyGrid
 
 KIND = 'region'
 
@@ -47,42 +45,11 @@ def default_box(lo, hi, cells, dilate):
     return (lo - pad * h).astype(np.float32), (hi + pad * h).astype(np.float32)
 
 
-class Region:
-    """A set of cells of an axis-aligned box, one bit per cell.  `words`: int32 [(cx cy cz + 31) // 32] on the device the
-    region is used on (a numpy array or CPU tensor is accepted where no kernel is called: save / load / fraction)."""
+class Region(BitGrid):
+    """A BitGrid whose set bits are the cells of the region; count() is their number."""
 
-    def __init__(self, bmin, bmax, cells, words):
-        self.bmin, self.bmax = mesh._bounds(bmin, bmax)
-        self.cells = _cells(cells)
-        self.inv = cell_inverse(self.bmin, self.bmax, self.cells)
-        if not (np.all(np.isfinite(self.inv)) and np.all(self.inv > 0)):
-            raise ValueError('the box is too thin or too large: cells / (bmax - bmin) is not a finite fp32 number')
-        if not torch.is_tensor(words):
-            words = torch.from_numpy(np.ascontiguousarray(np.asarray(words)))
-        n = ops.occupancy_words(self.cells)
-        if words.dtype != torch.int32 or tuple(words.shape) != (n,):
-            raise ValueError(f'words must be int32 [{n}] for cells {self.cells}, got {words.dtype} {tuple(words.shape)}')
-        self.words = words.contiguous()
-
-    @property
-    def device(self):
-        return self.words.device
-
-    @property
-    def n_cells(self):
-        return self.cells[0] * self.cells[1] * self.cells[2]
-
-    def box(self):
-        """(bmin, inv) as the six floats the kernels take."""
-        return [float(v) for v in self.bmin] + [float(v) for v in self.inv]
-
-    def to(self, device):
-        return Region(self.bmin, self.bmax, self.cells, self.words.to(device))
-
-    def count(self):
-        """Number of cells in the region."""
-        w = self.words.detach().cpu().numpy().view(np.uint32)
-        return int(np.unpackbits(w.view(np.uint8)).sum())
+    KIND = KIND
+    NOUN = 'a region'
 
     def fraction(self):
         """Share of the box's cells that are in the region."""
@@ -126,29 +93,6 @@ class Region:
         if tail:
             words[-1] &= (1 << tail) - 1
         return OccupancyGrid(self.bmin, self.bmax, self.cells, words)
-
-    def save(self, path):
-        """An .npz as occupancy's (words, bmin, bmax, cells, inv, version) plus kind = 'region'."""
-        np.savez(path, words=self.words.detach().cpu().numpy(), bmin=self.bmin, bmax=self.bmax,
-                 cells=np.asarray(self.cells, np.int32), inv=self.inv, version=np.asarray([FORMAT_VERSION], np.int32),
-                 kind=np.asarray(KIND))
-
-    @classmethod
-    def load(cls, path, device=None):
-        with np.load(path, allow_pickle=False) as d:
-            missing = [k for k in ('words', 'bmin', 'bmax', 'cells', 'inv', 'version') if k not in d.files]
-            if missing:
-                raise ValueError(f'{path}: not a region file (missing {missing})')
-            if 'kind' not in d.files or str(d['kind']) != KIND:
-                raise ValueError(f"{path}: not a region file (no kind = '{KIND}'; an occupancy grid means the opposite "
-                                 f'outside its box and is not read as a region)')
-            if int(d['version'][0]) != FORMAT_VERSION:
-                raise ValueError(f'{path}: format version {int(d["version"][0])}, expected {FORMAT_VERSION}')
-            words, bmin, bmax, cells, inv = d['words'], d['bmin'], d['bmax'], d['cells'], d['inv']
-        r = cls(bmin, bmax, tuple(int(c) for c in cells), torch.from_numpy(words.astype(np.int32, copy=False)))
-        if not np.array_equal(r.inv, inv.astype(np.float32)):
-            raise ValueError(f'{path}: stored cell scale {inv.tolist()} differs from the one its box gives {r.inv.tolist()}')
-        return r if device is None else r.to(device)
 
     @classmethod
     def from_points(cls, pts, bmin=None, bmax=None, cells=64, dilate=1):

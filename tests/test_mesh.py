@@ -94,6 +94,31 @@ def test_empty_surfaces_and_nonfinite_grid(cuda):
         mesh.marching_cubes(g, 1.0, (-1, -1, -1), (1, 1, 1))
 
 
+def two_far_spheres(x, y, z):
+    d1 = np.sqrt((x - 20.3) ** 2 + (y - 30.7) ** 2 + (z - 7.4) ** 2)
+    d2 = np.sqrt((x - 740.3) ** 2 + (y - 700.7) ** 2 + (z - 8.6) ** 2)
+    return 2.0 - np.minimum(d1, d2) / 6.0
+
+
+def test_scan_carry_past_one_chunk_matches_restatement(cuda):
+    """9216 workgroups: the scan of the workgroup totals runs a second 8192-record chunk.  One sphere lies in the first
+    chunk's points, the other past workgroup 8192, so the second sphere's vertex ids and face slots are right only if both
+    carried totals (vertices, triangles) are."""
+    shape, lo, hi = (768, 768, 16), (0, 0, 0), (767, 767, 15)
+    grid = field(shape, lo, hi, two_far_spheres)
+    ins = grid >= 1.0
+    crossing = np.zeros(shape, bool)                       # points that own a crossing edge (+x, +y, +z)
+    crossing[:-1] |= ins[:-1] != ins[1:]
+    crossing[:, :-1] |= ins[:, :-1] != ins[:, 1:]
+    crossing[:, :, :-1] |= ins[:, :, :-1] != ins[:, :, 1:]
+    n = np.nonzero(crossing.reshape(-1))[0]
+    split = 8192 * 1024
+    assert grid.size == 9216 * 1024 and (n < split).sum() == 508 and (n >= split).sum() == 508
+    v, f, _ = compare(grid, 1.0, lo, hi, cuda)
+    assert v.shape == (1384, 3) and f.shape == (2760, 3)
+    assert M.is_closed(f.cpu().numpy())
+
+
 def test_sphere_129_closed(cuda):
     r = 0.6
     lo, hi = (-1, -1, -1), (1, 1, 1)

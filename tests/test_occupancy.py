@@ -172,7 +172,8 @@ def test_lookup_equals_restatement(cuda):
     assert 0.3 < want.mean() < 0.9
 
 
-@pytest.mark.parametrize('B,S', [(1, 64), (777, 64), (5000, 128), (16, 2), (1031, 7)])
+# (66000, 128): 8250 workgroups, the smallest round size past one 8192-count chunk of the scan of the workgroup counts
+@pytest.mark.parametrize('B,S', [(1, 64), (777, 64), (5000, 128), (16, 2), (1031, 7), (66000, 128)])
 def test_mark_and_compact_equal_restatement(B, S, cuda):
     occ = random_cells(CELLS, seed=B)
     g = make_grid(occ, cuda)
@@ -186,6 +187,8 @@ def test_mark_and_compact_equal_restatement(B, S, cuda):
     np.testing.assert_array_equal(N(mask).reshape(-1).astype(bool), want)
     np.testing.assert_array_equal(N(idx), np.nonzero(want)[0])                   # ascending
     assert K == int(want.sum()) == idx.shape[0]
+    if B * S > 8192 * 1024:
+        assert N(idx)[-1] >= 8192 * 1024                                         # the carry into the second chunk decides an output
     np.testing.assert_array_equal(N(pts), N(full).reshape(-1, 3)[N(idx)])
     np.testing.assert_array_equal(N(dirs), N(rows)[N(idx) // S, 8:11])
     ref = N(rows[:, None, 0:3] + rows[:, None, 3:6] * z[:, :, None])

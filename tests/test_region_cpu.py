@@ -123,6 +123,8 @@ def test_carve_is_the_complement_with_zero_tail_bits():
     r = Region((0, 0, 0), (1, 1, 1), cells, R.pack(reg))
     grid = r.carve()
     assert isinstance(grid, OccupancyGrid) and grid.cells == cells
+    # the two types share a base and nothing else: carve() and to() give each its own
+    assert type(grid) is OccupancyGrid and type(r.to('cpu')) is Region and type(grid.to('cpu')) is OccupancyGrid
     np.testing.assert_array_equal(grid.words.numpy(), words)
     np.testing.assert_array_equal(grid.bmin, r.bmin)
     np.testing.assert_array_equal(grid.inv, r.inv)
