@@ -775,6 +775,41 @@ int mvip_region_lookup(const float *pts, int64_t P, const float *box, const int 
                        void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Connected components of a bit array (beyond the reference, which has no geometry clean-up;
+ * csrc/components.hip, mvip_nerf_amd/bitgrid.py and mesh.py).  The array is [nx,ny,nz], z fastest,
+ * 1 <= n <= 768 per axis (the cells of a grid above, or the lattice points of marching cubes); element
+ * l = (i*ny + j)*nz + k is bit l & 31 of int32 word l >> 5, (nx*ny*nz + 31) / 32 words in DEVICE
+ * memory, unused tail bits zero.  Two set elements are neighbours at connectivity 6 if they differ by
+ * one step on one axis, at connectivity 26 if by at most one step on every axis; a neighbour exists
+ * only inside the array.  Components are numbered 1, 2, ... by ascending lowest linear index of their
+ * elements.
+ *
+ * mvip_components_pack: values [n] fp32 -> words [(n + 31) / 32], bit l = values[l] >= threshold (NaN
+ *   value: clear); 0 <= n <= 768^3, threshold not NaN.  n == 0: MVIP_OK, nothing launched.
+ * mvip_components_groups: G, the workgroup count of an array (-1 for a shape outside the limits).
+ * mvip_components_label: union-find over the set elements; parent [nx*ny*nz] int32 receives -1 for a
+ *   clear bit and else the lowest linear index of the element's component, wg [G] int32 the exclusive
+ *   offsets of the component roots of each workgroup, total [1] int64 the number of components; the
+ *   caller reads total back once to allocate mvip_components_rank's outputs.  connectivity: 6 or 26.
+ *   The unions use a vector atomic minimum; every link points to a lower index, so the root of a
+ *   component is its lowest index whatever order the unions ran in and the outputs are reproducible
+ *   bit for bit.
+ * mvip_components_rank: from label's parent / wg and n_components: labels [nx*ny*nz] int32 (0 for a
+ *   clear bit, else the component's number), sizes [n_components] int32 (integer atomic adds: exact
+ *   in any order), first [n_components] int32 (lowest linear index).  n_components == 0: MVIP_OK,
+ *   nothing launched or written.
+ * mvip_components_select: labels [n] and keep [n_components + 1] uint8 (keep[0] is not read: label 0
+ *   is never kept) -> words [(n + 31) / 32]: bit l set iff keep[labels[l]] != 0.  n == 0: MVIP_OK,
+ *   nothing launched. */
+int mvip_components_pack(const float *values, int64_t n, float threshold, int *words, void *stream);
+int64_t mvip_components_groups(int nx, int ny, int nz);
+int mvip_components_label(const int *words, int nx, int ny, int nz, int connectivity, int *parent, int *wg, int64_t *total,
+                          void *stream);
+int mvip_components_rank(const int *parent, int nx, int ny, int nz, const int *wg, int64_t n_components, int *labels,
+                         int *sizes, int *first, void *stream);
+int mvip_components_select(const int *labels, int64_t n, const void *keep, int64_t n_components, int *words, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Ray distortion loss (mip-NeRF 360, eq. 15; beyond the reference, which has no regulariser of this kind and
  * no call site this replaces; csrc/distortion.hip).  rows [B,ncols] (ncols 8 or 11; near = column 6,
  * far = column 7), z [B,S] in ascending order along the ray, weights [B,S].

@@ -177,6 +177,11 @@ _SIGNATURES = {
     'mvip_region_mark': (_int, [_c_f, _i64, ctypes.POINTER(_flt), ctypes.POINTER(_int), _c_f, _c_f]),
     'mvip_region_accumulate': (_int, [_c_f, _c_f, _c_f, _i64, _int, ctypes.POINTER(_flt), ctypes.POINTER(_int), _c_f, _c_f, _c_f]),
     'mvip_region_lookup': (_int, [_c_f, _i64, ctypes.POINTER(_flt), ctypes.POINTER(_int), _c_f, _c_f, _c_f]),
+    'mvip_components_pack': (_int, [_c_f, _i64, _flt, _c_f, _c_f]),
+    'mvip_components_groups': (_i64, [_int, _int, _int]),
+    'mvip_components_label': (_int, [_c_f, _int, _int, _int, _int, _c_f, _c_f, _c_f, _c_f]),
+    'mvip_components_rank': (_int, [_c_f, _int, _int, _int, _c_f, _i64, _c_f, _c_f, _c_f, _c_f]),
+    'mvip_components_select': (_int, [_c_f, _i64, _c_f, _i64, _c_f, _c_f]),
     'mvip_distortion_loss': (_int, [_c_f, _int, _c_f, _c_f, _i64, _int, _int, _c_f, _c_f, _c_f]),
     'mvip_harmonic_tiles': (_i64, [_int, _int]),
     'mvip_harmonic_workspace_bytes': (_i64, [_i64, _int, _int]),

@@ -75,6 +75,47 @@ class BitGrid:
         w = self.words.detach().cpu().numpy().view(np.uint32)
         return int(np.unpackbits(w.view(np.uint8)).sum())
 
+    def components(self, connectivity=6):
+        """Connected components of the set cells (ops.grid_components, csrc/components.hip): (labels [cx, cy, cz] int32,
+        sizes [n] int32, first [n] int32), all on the grid's device.  labels is 0 for a clear bit, else the 1-based number
+        of the cell's component, numbered by ascending lowest linear cell (`first`).  connectivity: 6 (cells that share a
+        face) or 26 (a face, an edge or a corner)."""
+        return ops.grid_components(self.words, self.cells, connectivity)
+
+    def _labels_at(self, labels, pts):
+        """Labels of the cells that pts [P, 3] fall in (cell_of's convention, in fp32 on the device); points outside the
+        box are left out."""
+        pts = torch.as_tensor(pts, dtype=torch.float32).reshape(-1, 3).to(self.device)
+        bmin = torch.from_numpy(self.bmin).to(self.device)
+        inv = torch.from_numpy(self.inv).to(self.device)
+        c = torch.tensor(self.cells, dtype=torch.float32, device=self.device)
+        f = torch.floor((pts - bmin) * inv)
+        inside = ((f >= 0) & (f < c)).all(-1)
+        i = f[inside].to(torch.int64)
+        return labels.reshape(-1)[(i[:, 0] * self.cells[1] + i[:, 1]) * self.cells[2] + i[:, 2]]
+
+    def keep_components(self, largest=None, min_cells=None, containing=None, connectivity=6):
+        """A new grid of the same type and box whose set bits are those of the kept components only.
+
+        largest = k: the k components with the most cells (ties: the lower `first`).  min_cells = m: components of at
+        least m cells.  Each of the two restricts the kept set: a component must meet both where both are given.
+        containing = pts [P, 3]: the components of the cells those points fall in (points outside the box or in a clear
+        cell name none), kept IN ADDITION to the restricted set.  ValueError for no criterion, k < 1 or m < 1.  The kept
+        set is chosen on the host from sizes / first (one small copy); the bits are written by ops.grid_select.
+
+        What dropping a component means is the subclass's.  An OccupancyGrid without its small islands renders the scene
+        WITHOUT them: the floaters are gone from the frame, not merely skipped, so the frame differs from the unskipped
+        render (unlike the grid from_model builds, which only skips what contributes nothing).  A Region without its
+        isolated cells no longer counts them as inside: stray marks far from the object stop masking pixels."""
+        if connectivity not in ops.CONNECTIVITIES:
+            raise ValueError(f'keep_components: connectivity must be 6 or 26, got {connectivity!r}')
+        largest, min_cells = ops.component_criteria('keep_components', largest, min_cells, containing is not None)
+        labels, sizes, _ = self.components(connectivity)
+        also = None if containing is None else self._labels_at(labels, containing).cpu().numpy()
+        keep = ops.component_keep_table(sizes.cpu().numpy(), largest, min_cells, also)
+        words = ops.grid_select(labels, torch.from_numpy(keep).to(self.device))
+        return type(self)(self.bmin, self.bmax, self.cells, words)
+
     def save(self, path):
         """An .npz of the words and the five small arrays (bmin, bmax, cells, inv, version), plus `kind` where the class
         has one."""

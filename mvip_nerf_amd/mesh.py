@@ -405,11 +405,40 @@ def vertex_colors(render_kwargs, verts, normals, network='fine', chunk=1 << 18):
     return rgb
 
 
+def remove_floaters(grid, threshold, largest=None, min_points=None, connectivity=6):
+    """A copy of the sigma lattice `grid` [nx, ny, nz] (device) with every lattice point of a dropped component set to 0,
+    which threshold > 0 makes "outside".  The components are those of the inside points (sigma >= threshold, the
+    predicate of marching_cubes; csrc/components.hip).  largest = k keeps the k components with the most points (ties:
+    the lower first point), min_points = m those of at least m points; a component must meet both where both are given.
+    ValueError for no criterion, k < 1, m < 1, a connectivity other than 6 or 26, threshold <= 0.
+
+    No lattice edge joins two different 6-components, so at connectivity 6 the crossing vertices of the kept components
+    keep their positions bit for bit, and their faces with them.  Normals are central differences of sigma: one may
+    differ where a dropped point lay within one lattice step of a kept vertex's edge."""
+    if not torch.is_tensor(grid):
+        raise ValueError('grid must be a torch tensor on the GPU')
+    _check_axes(grid.shape)
+    threshold = float(threshold)
+    if not (threshold > 0 and math.isfinite(threshold)):
+        raise ValueError(f'threshold must be finite and > 0, got {threshold}')
+    if connectivity not in ops.CONNECTIVITIES:
+        raise ValueError(f'remove_floaters: connectivity must be 6 or 26, got {connectivity!r}')
+    largest, min_points = ops.component_criteria('remove_floaters', largest, min_points, size_name='min_points')
+    labels, sizes, _ = ops.grid_components(ops.grid_pack(grid, threshold), grid.shape, connectivity)
+    keep = ops.component_keep_table(sizes.cpu().numpy(), largest, min_points)
+    kept = torch.from_numpy(keep).to(grid.device)[labels.to(torch.int64)].bool()
+    return torch.where(kept | (labels == 0), grid, torch.zeros((), device=grid.device, dtype=grid.dtype))
+
+
 def extract_mesh(render_kwargs, bound_min, bound_max, resolution=256, threshold=10.0, colors=True, network='fine',
-                 chunk=1 << 18):
+                 chunk=1 << 18, largest=None, min_points=None):
     """Mesh(verts, faces, normals, colors) of the surface sigma = threshold inside the box: marching_cubes(density_grid(...)),
-    colours from vertex_colors() (uint8 [V, 3]), or None with colors=False."""
+    colours from vertex_colors() (uint8 [V, 3]), or None with colors=False.  largest / min_points (default None: the
+    lattice goes to marching cubes as it is): remove_floaters() on the lattice first, at connectivity 6 -- the table cuts
+    diagonal inside corners off separately, so the sheets of the mesh follow the 6-components of the inside points."""
     grid = density_grid(render_kwargs, bound_min, bound_max, resolution, network, chunk)
+    if largest is not None or min_points is not None:
+        grid = remove_floaters(grid, threshold, largest, min_points, connectivity=6)
     verts, faces, normals = marching_cubes(grid, threshold, bound_min, bound_max)
     rgb = vertex_colors(render_kwargs, verts, normals, network, chunk) if colors else None
     return Mesh(verts, faces, normals, rgb)

@@ -30,7 +30,9 @@ def _threshold(threshold):
 
 
 class OccupancyGrid(BitGrid):
-    """A BitGrid whose set bits are the occupied cells."""
+    """A BitGrid whose set bits are the occupied cells.  keep_components() (bitgrid.py) gives a grid without the dropped
+    islands: rendering with it shows the scene WITHOUT them -- a different frame, the floaters gone from it, not merely
+    skipped."""
 
     NOUN = 'an occupancy grid'
 

@@ -1933,6 +1933,114 @@ def region_lookup(pts, box, cells, words):
     return _grid_lookup('region_lookup', pts, box, cells, words)
 
 
+# connected components of a bit array (beyond the reference, csrc/components.hip; bitgrid.py and mesh.py use them) --------
+# The array is [nx, ny, nz], z fastest, 1..768 per axis, in the bit layout of the grids above.
+
+CONNECTIVITIES = (6, 26)
+MAX_COMPONENT_AXIS = 768
+
+
+def _component_shape(who, shape, connectivity=6):
+    if connectivity not in CONNECTIVITIES:
+        raise ValueError(f'{who}: connectivity must be 6 or 26, got {connectivity!r}')
+    shape = tuple(int(s) for s in shape)
+    if len(shape) != 3 or not all(1 <= s <= MAX_COMPONENT_AXIS for s in shape):
+        raise _lib.MvipError(f'{who}: shape {shape} outside three axes of 1..{MAX_COMPONENT_AXIS}')
+    return shape
+
+
+def grid_pack(values, threshold):
+    """fp32 values (any shape, at most 768^3 elements) on the device -> int32 words [(n + 31) // 32]: bit l of the
+    flattened array = values[l] >= threshold (NaN: clear), tail bits zero."""
+    v = _f32c(values).reshape(-1)
+    n = v.shape[0]
+    threshold = float(threshold)
+    if threshold != threshold or n > MAX_COMPONENT_AXIS ** 3:
+        raise _lib.MvipError(f'grid_pack: {n} values, threshold {threshold} (at most 768^3 values, threshold not NaN)')
+    words = torch.empty((n + 31) // 32, device=v.device, dtype=_I32)
+    call('mvip_components_pack', ptr(v), n, threshold, ptr(words, _I32), stream())
+    return words
+
+
+def grid_components(words, shape, connectivity=6):
+    """Connected components of the set bits of `words` read as an array of `shape` = (nx, ny, nz): (labels [nx, ny, nz]
+    int32, sizes [n] int32, first [n] int32).  labels is 0 where the bit is clear and else the 1-based number of the
+    element's component; components are numbered by ascending lowest linear index (`first`), the order of
+    scipy.ndimage.label.  connectivity 6 (faces) or 26 (the 3 x 3 x 3 neighbourhood).  With no set bit labels is all zeros
+    and sizes / first are empty.  Reads the number of components back once (the only synchronisation)."""
+    nx, ny, nz = _component_shape('grid_components', shape, connectivity)
+    n = nx * ny * nz
+    if tuple(words.shape) != ((n + 31) // 32,):
+        raise _lib.MvipError(f'grid_components: {tuple(words.shape)} words for shape {(nx, ny, nz)}')
+    dev = words.device
+    G = _lib.load().mvip_components_groups(nx, ny, nz)
+    parent = torch.empty(n, device=dev, dtype=_I32)
+    wg = torch.empty(G, device=dev, dtype=_I32)
+    total = torch.empty(1, device=dev, dtype=torch.int64)
+    call('mvip_components_label', ptr(words, _I32), nx, ny, nz, int(connectivity), ptr(parent, _I32), ptr(wg, _I32),
+         ptr(total, torch.int64), stream())
+    nc = int(total.cpu())
+    sizes = torch.empty(nc, device=dev, dtype=_I32)
+    first = torch.empty(nc, device=dev, dtype=_I32)
+    if nc == 0:
+        return torch.zeros((nx, ny, nz), device=dev, dtype=_I32), sizes, first
+    labels = torch.empty((nx, ny, nz), device=dev, dtype=_I32)
+    call('mvip_components_rank', ptr(parent, _I32), nx, ny, nz, ptr(wg, _I32), nc, ptr(labels, _I32), ptr(sizes, _I32),
+         ptr(first, _I32), stream())
+    return labels, sizes, first
+
+
+def grid_select(labels, keep):
+    """labels (int32, any shape) and keep uint8 [n_components + 1] (keep[0] = 0) -> int32 words of exactly the elements
+    whose component is kept, tail bits zero."""
+    lab = labels.contiguous().reshape(-1)
+    n = lab.shape[0]
+    if keep.dim() != 1 or keep.shape[0] < 1 or keep.shape[0] - 1 > n or n > MAX_COMPONENT_AXIS ** 3:
+        raise _lib.MvipError(f'grid_select: keep {tuple(keep.shape)} for {n} labels')
+    if keep.shape[0] == 1 or n == 0:
+        return torch.zeros((n + 31) // 32, device=lab.device, dtype=_I32)
+    words = torch.empty((n + 31) // 32, device=lab.device, dtype=_I32)
+    call('mvip_components_select', ptr(lab, _I32), n, ptr(keep.contiguous(), torch.uint8), keep.shape[0] - 1, ptr(words, _I32),
+         stream())
+    return words
+
+
+def component_criteria(who, largest, min_size, other=False, size_name='min_cells'):
+    """The checked (largest, min_size) of a keep-components call: each None or an integer >= 1, and at least one criterion
+    given (`other`: the caller has one of its own).  ValueError otherwise; nothing is launched."""
+    for name, v in (('largest', largest), (size_name, min_size)):
+        if v is not None and (int(v) != v or int(v) < 1):
+            raise ValueError(f'{who}: {name} must be an integer >= 1, got {v!r}')
+    if largest is None and min_size is None and not other:
+        raise ValueError(f'{who}: no criterion given: name the components to keep (largest, {size_name}, ...)')
+    return (None if largest is None else int(largest)), (None if min_size is None else int(min_size))
+
+
+def component_keep_table(sizes, largest=None, min_size=None, also=None):
+    """keep uint8 [n + 1] (host numpy; keep[0] = 0) over components 1..n of sizes [n] (host, in label order, i.e. by
+    ascending lowest index).  largest = k: the k components with the most elements, ties to the lower label (= the lower
+    `first`); min_size = m: components of at least m elements; a component must meet every criterion given.  also: labels
+    kept in any case (OR-ed in; 0 and out-of-range entries ignored).  With neither criterion only `also` is kept."""
+    import numpy as np
+    sizes = np.asarray(sizes, np.int64)
+    n = sizes.shape[0]
+    kept = np.zeros(n, bool)
+    if largest is not None or min_size is not None:
+        kept[:] = True
+        if min_size is not None:
+            kept &= sizes >= min_size
+        if largest is not None:
+            top = np.zeros(n, bool)
+            top[np.argsort(-sizes, kind='stable')[:largest]] = True
+            kept &= top
+    if also is not None:
+        a = np.asarray(also, np.int64).reshape(-1)
+        kept[a[(a >= 1) & (a <= n)] - 1] = True
+    table = np.zeros(n + 1, np.uint8)
+    table[1:] = kept
+    return table
+
+
 # ray distortion loss (mip-NeRF 360 eq. 15; beyond the reference, csrc/distortion.hip) ------------------------------------------
 
 class _DistortionLoss(torch.autograd.Function):

@@ -46,7 +46,8 @@ def default_box(lo, hi, cells, dilate):
 
 
 class Region(BitGrid):
-    """A BitGrid whose set bits are the cells of the region; count() is their number."""
+    """A BitGrid whose set bits are the cells of the region; count() is their number.  keep_components() (bitgrid.py)
+    gives a region whose isolated marked cells no longer count as inside."""
 
     KIND = KIND
     NOUN = 'a region'

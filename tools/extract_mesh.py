@@ -4,6 +4,11 @@ binary PLY (mvip_nerf_amd/mesh.py).  Prints sigma percentiles of the grid (to ch
 
   python tools/extract_mesh.py CKPT.tar --out mesh.ply [--model mlp|tcnn] [--bound-min x y z --bound-max x y z]
          [--resolution 256] [--threshold 10] [--network fine|coarse] [--precision fp32|split] [--no-colors]
+         [--keep-largest K] [--min-component N]
+
+--keep-largest K keeps the K largest connected components of the inside lattice points, --min-component N those of at
+least N points (mesh.remove_floaters, connectivity 6; both: a component must meet both); the counts before and after are
+printed.
 """
 import argparse
 import os
@@ -18,7 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-from mvip_nerf_amd import mesh, run                                          # noqa: E402
+from mvip_nerf_amd import mesh, ops, run                                       # noqa: E402
 
 
 def model_args(n_importance):
@@ -54,6 +59,8 @@ def main(argv=None):
     ap.add_argument('--network', choices=('fine', 'coarse'), default='fine')
     ap.add_argument('--precision', choices=('fp32', 'split'), default='fp32', help='MLP query precision (mlp model)')
     ap.add_argument('--no-colors', action='store_true')
+    ap.add_argument('--keep-largest', type=int, default=None, metavar='K', help='keep the K largest components')
+    ap.add_argument('--min-component', type=int, default=None, metavar='N', help='drop components below N lattice points')
     a = ap.parse_args(argv)
     res = a.resolution[0] if len(a.resolution) == 1 else tuple(a.resolution)
     dev = torch.device('cuda', 0)
@@ -74,11 +81,17 @@ def main(argv=None):
     q = np.percentile(grid.float().cpu().numpy(), [1, 5, 25, 50, 75, 95, 99])
     print(f'checkpoint {a.ckpt} (step {step}, model {a.model}, {a.network} network), grid {tuple(grid.shape)}')
     print('sigma percentiles  ' + '  '.join(f'p{p}={v:.4g}' for p, v in zip((1, 5, 25, 50, 75, 95, 99), q)))
+    t_cc = 0.0
+    if a.keep_largest is not None or a.min_component is not None:
+        n_before = int(ops.grid_components(ops.grid_pack(grid, a.threshold), grid.shape)[1].shape[0])
+        grid, t_cc = timed(lambda: mesh.remove_floaters(grid, a.threshold, a.keep_largest, a.min_component))
+        n_after = int(ops.grid_components(ops.grid_pack(grid, a.threshold), grid.shape)[1].shape[0])
+        print(f'components of the inside points: {n_before} -> {n_after} kept')
     (verts, faces, normals), t_mc = timed(lambda: mesh.marching_cubes(grid, a.threshold, a.bound_min, a.bound_max))
     colors, t_col = (None, 0.0) if a.no_colors else timed(lambda: mesh.vertex_colors(kw, verts, normals, a.network))
     _, t_ply = timed(lambda: mesh.save_ply(a.out, mesh.Mesh(verts, faces, normals, colors)))
     print(f'threshold {a.threshold}: {verts.shape[0]} vertices, {faces.shape[0]} triangles -> {a.out}')
-    print(f'time  density grid {t_grid * 1e3:.1f} ms  marching cubes {t_mc * 1e3:.1f} ms  colours {t_col * 1e3:.1f} ms  '
+    print(f'time  density grid {t_grid * 1e3:.1f} ms  components {t_cc * 1e3:.1f} ms  marching cubes {t_mc * 1e3:.1f} ms  colours {t_col * 1e3:.1f} ms  '
           f'write {t_ply * 1e3:.1f} ms')
     return 0
 

@@ -7,7 +7,9 @@ into a region through the trained field's ray weights, render the region into ev
 --fixture trains the scene-1 fixture (tests/golden/scene1_small.npz, the 1,500-iteration recipe of
 tools/render_occupancy_ab.py::train_scene1) and annotates with the fixture's own masks; --checkpoint / --datadir load a
 model in the reference's .tar format and a SPIn-NeRF style scene, and annotate with the scene's label/*.png of the views
-named.  --views may be repeated: one run per annotated set, the field trained or loaded once.
+named.  --views may be repeated: one run per annotated set, the field trained or loaded once.  --keep-largest K keeps
+only the K largest connected components of the lifted region (BitGrid.keep_components, connectivity 6) before it is
+propagated; the JSON then carries the cell and component counts before the cut as well.
 
 Per set, into DIR/views_<set>/: label/NNNNNN.png (0 / 255, one per view, the layout load_llff._load_data reads; with
 --datadir the scene's own file names), region.npz (Region.save), with --carve-preview VIEW that view rendered with and
@@ -88,6 +90,7 @@ def main(argv=None):
     ap.add_argument('--dilate', type=int, default=1)
     ap.add_argument('--min-weight', type=float, default=None)
     ap.add_argument('--threshold', type=float, default=0.5)
+    ap.add_argument('--keep-largest', type=int, default=None, metavar='K', help='keep the K largest components of the region')
     ap.add_argument('--carve-preview', type=int, default=None, metavar='VIEW')
     a = ap.parse_args(argv)
     if a.fixture == bool(a.checkpoint) or bool(a.checkpoint) != bool(a.datadir):
@@ -117,6 +120,11 @@ def main(argv=None):
         os.makedirs(os.path.join(folder, 'label'), exist_ok=True)
         region, t_lift = timed(lambda: Region.from_masks(te, hwf, poses[annotated], torch.from_numpy(masks[annotated]).to(dev),
                                                          near, far, cells=a.cells, min_weight=a.min_weight, dilate=a.dilate))
+        lifted = None
+        if a.keep_largest is not None:
+            lifted = {'region_cells_lifted': region.count(), 'region_components_lifted': int(region.components()[1].shape[0]),
+                      'keep_largest': a.keep_largest}
+            region, lifted['seconds_keep_components'] = timed(lambda: region.keep_components(largest=a.keep_largest))
         (soft, hard), t_prop = timed(lambda: propagate_masks(te, hwf, poses, region, near, far, a.threshold))
         hard = hard.cpu().numpy()
         region.save(os.path.join(folder, 'region.npz'))
@@ -132,6 +140,7 @@ def main(argv=None):
                'copy_baseline_mean': float(np.mean(list(base.values()))), 'copy_baseline_min': float(np.min(list(base.values()))),
                'mean_iou_annotated_views': float(np.mean([ious[v] for v in annotated])),
                'seconds_lift': t_lift, 'seconds_propagate_all_views': t_prop}
+        rec.update(lifted or {})
         if a.carve_preview is not None:
             with torch.no_grad():
                 kw = dict(te, near=near, far=far)
