@@ -911,6 +911,41 @@ int mvip_ssim_forward(const float *x, const float *y, const void *mask, int64_t 
 int mvip_ssim_backward(const float *x, const float *y, const float *stash, const float *gout, const int *count, int64_t N,
                        int H, int W, int C, float *gx, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Exemplar-based (PatchMatch) image inpainting (beyond the reference, whose RGB_inpainted/ images are made elsewhere;
+ * csrc/exemplar.hip, ops.exemplar_fill, prepare.inpaint_views).  A pyramid, then nearest-neighbour-field search
+ * alternating with voting, coarse to fine, in integers on 8-bit colours; the definition is written out in
+ * csrc/exemplar.hip and tests/exemplar_numpy.py, which agree bit for bit.  All operands DEVICE memory, dense:
+ *   images [N,H,W,3] fp32, masks [N,H,W] bytes (0 / non-zero), sources [N,H,W] bytes or NULL (every known pixel
+ *   may serve as an exemplar), out [N,H,W,3] fp32 (not images), nnf [N,H,W,2] int32 = (sy, sx) or -1 off the targets.
+ * The caller provides workspace (mvip_exemplar_workspace_bytes bytes), meta (mvip_exemplar_meta_words int32 words,
+ * 8-byte aligned) and, after reading meta back once, lists (int32).  meta: words 0..47 = totals[level][c] as int64
+ * (c: 0 targets, 1 hole pixels, 2 sources; over the batch), 48..95 = where each list starts, then 32 words per
+ * image: 0 levels used (0: singular, no source at level 0: returned unchanged), 1 singular, 2..3 the energy (uint64:
+ * the summed SSD of the final field), 4 + 3 level + c the image's counts.
+ * mvip_exemplar_levels: the pyramid's level count from the geometry (levels are added while min(h,w)/2 >= 4 patch;
+ *   max_levels 0: no cap beyond 8), -1 for a bad shape.  It is the `levels` of the other entry points.
+ * mvip_exemplar_setup: quantise, build the pyramid and the target / source sets, count them, plan.
+ * mvip_exemplar_lists: the compacted lists; capacity = the sum of all totals (or more).
+ * mvip_exemplar_level: one level's schedule (initial field, vote, rounds x (iters searches, vote); at level 0 the
+ *   energy); call it for level = levels - 1 down to 0 with n_targets / n_holes = that level's totals, and the same
+ *   rounds, iters and seed throughout.  Both totals 0: nothing launched.
+ * mvip_exemplar_finish: out and nnf.
+ * patch odd in 3..9, patch <= H, W <= 16384, N >= 0, 1 <= levels <= mvip_exemplar_levels(H,W,patch,0), the pixels of all
+ * levels of the batch <= (2^31 - 1) / 4, rounds, iters >= 0, else MVIP_EINVAL (-1 from the size queries) before anything is
+ * touched; N == 0: MVIP_OK, nothing launched; with N > 0 a NULL operand other than sources is MVIP_EINVAL. */
+int mvip_exemplar_levels(int H, int W, int patch, int max_levels);
+int64_t mvip_exemplar_meta_words(int64_t N);
+int64_t mvip_exemplar_workspace_bytes(int64_t N, int H, int W, int patch, int levels);
+int mvip_exemplar_setup(const float *images, const void *masks, const void *sources, int64_t N, int H, int W, int patch,
+                        int levels, void *workspace, int *meta, void *stream);
+int mvip_exemplar_lists(int64_t N, int H, int W, int patch, int levels, void *workspace, const int *meta, int *lists,
+                        int64_t capacity, void *stream);
+int mvip_exemplar_level(int64_t N, int H, int W, int patch, int levels, int level, int64_t n_targets, int64_t n_holes,
+                        int rounds, int iters, unsigned seed, void *workspace, int *meta, const int *lists, void *stream);
+int mvip_exemplar_finish(const float *images, int64_t N, int H, int W, int patch, int levels, int rounds, int iters,
+                         void *workspace, const int *meta, float *out, int *nnf, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -194,6 +194,13 @@ _SIGNATURES = {
     'mvip_ssim_tiles': (_i64, [_int, _int]),
     'mvip_ssim_forward': (_int, [_c_f, _c_f, _c_f, _i64, _int, _int, _int, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f]),
     'mvip_ssim_backward': (_int, [_c_f, _c_f, _c_f, _c_f, _c_f, _i64, _int, _int, _int, _c_f, _c_f]),
+    'mvip_exemplar_levels': (_int, [_int, _int, _int, _int]),
+    'mvip_exemplar_meta_words': (_i64, [_i64]),
+    'mvip_exemplar_workspace_bytes': (_i64, [_i64, _int, _int, _int, _int]),
+    'mvip_exemplar_setup': (_int, [_c_f, _c_f, _c_f, _i64, _int, _int, _int, _int, _c_f, _c_f, _c_f]),
+    'mvip_exemplar_lists': (_int, [_i64, _int, _int, _int, _int, _c_f, _c_f, _c_f, _i64, _c_f]),
+    'mvip_exemplar_level': (_int, [_i64, _int, _int, _int, _int, _int, _i64, _i64, _int, _int, ctypes.c_uint, _c_f, _c_f, _c_f, _c_f]),
+    'mvip_exemplar_finish': (_int, [_c_f, _i64, _int, _int, _int, _int, _int, _int, _c_f, _c_f, _c_f, _c_f, _c_f]),
 }
 
 # every symbol include/mvip_nerf.h declares; tests check the built library exports all of them

@@ -2318,3 +2318,85 @@ def ssim(x, y, mask=None, return_map=False, return_count=False):
     res = _Ssim.apply(x, y.detach(), mask, bool(return_map))
     out = (res[0],) + ((res[2],) if return_map else ()) + ((res[1].detach(),) if return_count else ())
     return out[0] if len(out) == 1 else out
+
+
+# exemplar-based (PatchMatch) image inpainting (beyond the reference, whose RGB_inpainted/ images are made elsewhere; csrc/exemplar.hip) --
+
+EXEMPLAR_META_HEADER = 96        # int32 words in front of the per-image state (csrc/exemplar.hip: META_STATE)
+EXEMPLAR_STATE_WORDS = 32
+EXEMPLAR_MAX_LEVELS = 8
+
+
+def exemplar_fill(images, masks, patch=7, rounds=3, iters=4, seed=0, sources=None, max_levels=None):
+    """Fill the masked (and the non-finite) pixels of images [N, H, W, 3] fp32 (0..1) with texture copied from the rest of the
+    same image: a pyramid, then nearest-neighbour-field search alternating with voting, coarse to fine, on 8-bit colours in
+    integer arithmetic (the definition is csrc/exemplar.hip's and tests/exemplar_numpy.py's; the two agree bit for bit).
+    masks [N, H, W] bool; sources [N, H, W] bool restricts the exemplars to patches that lie wholly inside it (None: every known
+    pixel); patch: the odd patch side in 3..9; per level `rounds` x (`iters` searches, one vote); max_levels caps the pyramid
+    (None: levels are added while min(h, w) // 2 >= 4 patch).  Returns (filled [N, H, W, 3], info).  Outside the hole the output
+    is the input bit for bit, inside it is k / 255.  info holds per image numpy arrays `targets`, `sources` (the sizes of the
+    two sets at full resolution), `levels` (the levels the image used), `energy` (the summed SSD of the final field, int64),
+    `singular` (no exemplar at full resolution: returned unchanged), and the device tensor `nnf` [N, H, W, 2] int32: (y, x) of each
+    target's exemplar, -1 off the targets.  The textures are plausible, not pixel-accurate: see DESIGN.md section 18.  One host
+    read-back sizes the lists and the per-level launches; info is read after the last launch.  Detached: no autograd."""
+    import numpy as np
+    what = 'exemplar_fill'
+    if not torch.is_tensor(images) or images.dtype != _F32 or images.dim() != 4 or images.shape[-1] != 3:
+        got = f'{tuple(images.shape)} {images.dtype}' if torch.is_tensor(images) else type(images).__name__
+        raise ValueError(f'{what}: images must be a {_F32} tensor [N, H, W, 3] on the GPU, got {got}')
+    v = images.detach()
+    m = _image_batch(what, masks, torch.bool, 'masks')
+    N, H, W, _ = v.shape
+    tensors = [v, m]
+    if tuple(m.shape) != (N, H, W):
+        raise ValueError(f'{what}: masks {tuple(m.shape)} for images {tuple(v.shape)}: [{N}, {H}, {W}] expected')
+    src = None
+    if sources is not None:
+        src = _image_batch(what, sources, torch.bool, 'sources')
+        if tuple(src.shape) != (N, H, W):
+            raise ValueError(f'{what}: sources {tuple(src.shape)} for images {tuple(v.shape)}: [{N}, {H}, {W}] expected')
+        tensors.append(src)
+    patch, rounds, iters, seed = int(patch), int(rounds), int(iters), int(seed)
+    if patch % 2 == 0 or not 3 <= patch <= 9:
+        raise ValueError(f'{what}: patch must be odd and in 3..9, got {patch}')
+    if min(H, W) < patch:
+        raise ValueError(f'{what}: images of {H} x {W} are smaller than the patch of {patch}')
+    if rounds < 0 or iters < 0:
+        raise ValueError(f'{what}: rounds {rounds} and iters {iters} must be >= 0')
+    if max_levels is not None and not 1 <= int(max_levels):
+        raise ValueError(f'{what}: max_levels must be >= 1 (or None), got {max_levels}')
+    if not 0 <= seed < 1 << 32:
+        raise ValueError(f'{what}: seed must be in 0 .. 2^32 - 1, got {seed}')
+    _on_gpu(what, *tensors)
+    if any(t.device != v.device for t in tensors):
+        raise ValueError(f'{what}: tensors on one device expected, got {sorted({str(t.device) for t in tensors})}')
+    if not all(t.is_contiguous() for t in tensors):
+        raise ValueError(f'{what}: every operand must be contiguous')
+    dev = v.device
+    out = torch.empty_like(v)
+    nnf = torch.empty((N, H, W, 2), device=dev, dtype=_I32)
+    if N == 0:
+        e = np.zeros(0, np.int64)
+        return out, {'targets': e, 'sources': e.copy(), 'levels': e.copy(), 'energy': e.copy(), 'singular': np.zeros(0, bool), 'nnf': nnf}
+    lib = _lib.load()
+    L = lib.mvip_exemplar_levels(H, W, patch, 0 if max_levels is None else min(int(max_levels), EXEMPLAR_MAX_LEVELS))
+    nbytes = lib.mvip_exemplar_workspace_bytes(N, H, W, patch, L) if L > 0 else -1
+    if nbytes < 0:
+        raise ValueError(f'{what}: {N} images of {H} x {W} are beyond the kernels\' index range')
+    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    meta = torch.empty(lib.mvip_exemplar_meta_words(N), device=dev, dtype=_I32)
+    st = stream()
+    pws, pmeta = ptr(ws, torch.uint8), ptr(meta, _I32)
+    call('mvip_exemplar_setup', ptr(v), ptr(m, torch.bool), ptr(src, torch.bool), N, H, W, patch, L, pws, pmeta, st)
+    totals = meta[:6 * EXEMPLAR_MAX_LEVELS].cpu().numpy().view(np.int64).reshape(EXEMPLAR_MAX_LEVELS, 3)     # the read-back
+    capacity = int(totals.sum())
+    lists = torch.empty(max(capacity, 1), device=dev, dtype=_I32)
+    call('mvip_exemplar_lists', N, H, W, patch, L, pws, pmeta, ptr(lists, _I32), capacity, st)
+    for level in range(L - 1, -1, -1):
+        call('mvip_exemplar_level', N, H, W, patch, L, level, int(totals[level, 0]), int(totals[level, 1]), rounds, iters, seed,
+             pws, pmeta, ptr(lists, _I32), st)
+    call('mvip_exemplar_finish', ptr(v), N, H, W, patch, L, rounds, iters, pws, pmeta, ptr(out), ptr(nnf, _I32), st)
+    s = meta[EXEMPLAR_META_HEADER:].cpu().numpy().reshape(N, EXEMPLAR_STATE_WORDS)
+    info = {'targets': s[:, 4].astype(np.int64), 'sources': s[:, 6].astype(np.int64), 'levels': s[:, 0].astype(np.int64),
+            'energy': np.ascontiguousarray(s[:, 2:4]).view(np.int64).reshape(N).copy(), 'singular': s[:, 1] != 0, 'nnf': nnf}
+    return out, info

@@ -17,7 +17,9 @@ keeps the precision that the 8-bit PNG of `write_llff` drops (one step of 1 / 25
 
 The third raster, `RGB_inpainted/`, comes from `propagate_reference`: one inpainted view (or a few) is
 carried into every other view by backward depth warping (`ops.warp_views`), what no reference sees is filled harmonically,
-and `write_images` writes the files.
+and `write_images` writes the files.  The inpainted reference itself can be made here too: `inpaint_views` fills the masks of
+the reference views with texture from the same image (`ops.exemplar_fill`; plausible, not pixel-accurate),
+and `propagate_reference(..., fill='exemplar')` uses the same fill for what no reference sees.
 """
 import os
 
@@ -117,6 +119,39 @@ def reference_order(poses, ref_views):
     return np.argsort(dist, axis=1, kind='stable').astype(np.int32)
 
 
+FILLS = {True: 'harmonic', False: 'none', 'harmonic': 'harmonic', 'exemplar': 'exemplar', 'none': 'none'}
+
+
+def inpaint_views(images, masks, views, method='exemplar', **kw):
+    """The `ref_images` of propagate_reference made from the dataset alone: images[views] with their masks filled by
+    ops.exemplar_fill (kw: patch, rounds, iters, seed, sources, max_levels).  images [N, H, W, 3] fp32 in 0..1, masks [N, H, W]
+    bool (tensors or arrays; the work is done on the device of `images` when that is a GPU tensor, else on 'cuda').  Returns
+    [len(views), H, W, 3] on the device.  ValueError for an unknown method, bad views, and a view with no exemplar."""
+    if method != 'exemplar':
+        raise ValueError(f'inpaint_views: method {method!r}: \'exemplar\' expected')
+    shape = lambda a: tuple(a.shape) if hasattr(a, 'shape') else type(a).__name__
+    if len(shape(images)) != 4 or shape(images)[-1] != 3:
+        raise ValueError(f'inpaint_views: images [N, H, W, 3] expected, got {shape(images)}')
+    N, H, W, _ = shape(images)
+    if shape(masks) != (N, H, W):
+        raise ValueError(f'inpaint_views: masks {shape(masks)} for images {shape(images)}: [{N}, {H}, {W}] expected')
+    views = [int(v) for v in views]
+    if not views or min(views) < 0 or max(views) >= N:
+        raise ValueError(f'inpaint_views: views {views}: at least one view of 0..{N - 1} expected')
+    device = images.device if torch.is_tensor(images) and images.is_cuda else torch.device('cuda')
+    pick = lambda a: a[views] if not torch.is_tensor(a) else a[torch.as_tensor(views, device=a.device)]
+    img = _to_device(pick(images), device, torch.float32)
+    msk = (torch.as_tensor(np.asarray(pick(masks)) if not torch.is_tensor(masks) else pick(masks)) != 0).to(device).contiguous()
+    if kw.get('sources') is not None:
+        s = kw['sources']
+        kw = dict(kw, sources=(torch.as_tensor(np.asarray(pick(s)) if not torch.is_tensor(s) else pick(s)) != 0).to(device).contiguous())
+    filled, info = ops.exemplar_fill(img, msk, **kw)
+    singular = [views[i] for i in np.nonzero(info['singular'])[0]]
+    if singular:
+        raise ValueError(f'inpaint_views: views {singular} have no exemplar (no patch free of masked pixels)')
+    return filled
+
+
 def propagate_reference(images, masks, disparities, poses, focal, ref_views, ref_images=None, tol=0.05, fill=True, **fill_kw):
     """Carry the inpainted reference views into every other view through geometry (beyond the reference, whose RGB_inpainted/
     images are independent 2D inpaintings): each masked pixel is lifted with its own disparity and looks its colour up in
@@ -130,14 +165,21 @@ def propagate_reference(images, masks, disparities, poses, focal, ref_views, ref
     Per target the references are tried in the order of reference_order.  The output image is `images` outside the mask bit
     for bit, the warped colour where a reference was taken, and on the remaining masked pixels (holes) the harmonic
     interpolant of the pixels around them, per channel, by one ops.harmonic_fill call over [3N, H, W] (fill=False leaves
-    `images` there; fill_kw: eps, max_iters, check_every, and allow_unconverged as in prepare_depths).  A view that is itself a
+    `images` there; fill_kw: eps, max_iters, check_every, and allow_unconverged as in prepare_depths).  fill='exemplar' fills
+    the holes with texture instead: one ops.exemplar_fill call over the N views with the holes as its masks and
+    sources = the pixels outside that view's mask, so that exemplars come from original pixels only (fill_kw: patch, rounds,
+    iters, seed, max_levels); 'harmonic' and 'none' are the names of True and False.  A view that is itself a
     reference takes its reference image unchanged (its masked pixels name itself as the source).
 
     Returns dict(images [N, H, W, 3], source [N, H, W] int32: -1 or the position in ref_views, resid [N, H, W], holes
     [N, H, W] bool = masks & (source < 0), coverage: numpy [N], the share of each view's masked pixels with a source (1 for
-    an empty mask), info: ops.harmonic_fill's over the planes 3 n + channel, None without fill).  ValueError for mismatched
-    shapes, an empty or invalid ref_views, and a plane with nothing to interpolate from; RuntimeError naming the views whose
+    an empty mask), info: ops.harmonic_fill's over the planes 3 n + channel, ops.exemplar_fill's over the views for
+    fill='exemplar', None without fill).  ValueError for mismatched shapes, an unknown fill, an empty or invalid ref_views, and
+    a plane (a view) with nothing to interpolate (copy) from; RuntimeError naming the views whose
     fill did not converge, unless allow_unconverged."""
+    if isinstance(fill, str) and fill not in FILLS:
+        raise ValueError(f'propagate_reference: fill {fill!r}: True / \'harmonic\', \'exemplar\' or False / \'none\' expected')
+    fill = FILLS[fill if isinstance(fill, str) else bool(fill)]
     allow_unconverged = bool(fill_kw.pop('allow_unconverged', False))
     device = images.device if torch.is_tensor(images) and images.is_cuda else torch.device('cuda')
     shape = lambda a: tuple(a.shape) if hasattr(a, 'shape') else type(a).__name__
@@ -172,7 +214,12 @@ def propagate_reference(images, masks, disparities, poses, focal, ref_views, ref
         source[v] = torch.where(msk[v], k, -1).to(source.dtype)
     holes = msk & (source < 0)
     info = None
-    if fill:
+    if fill == 'exemplar':
+        out, info = ops.exemplar_fill(out.contiguous(), holes.contiguous(), sources=(~msk).contiguous(), **fill_kw)
+        singular = np.nonzero(info['singular'])[0].tolist()
+        if singular:
+            raise ValueError(f'propagate_reference: views {singular} have no exemplar outside their masks to fill their holes from')
+    elif fill == 'harmonic':
         planes = out.permute(0, 3, 1, 2).reshape(3 * N, H, W).contiguous()
         filled, info = ops.harmonic_fill(planes, holes[:, None].expand(N, 3, H, W).reshape(3 * N, H, W).contiguous(), **fill_kw)
         singular = sorted({int(p) // 3 for p in np.nonzero(info['singular'])[0]})

@@ -4,10 +4,14 @@ depth warping, fill what no reference sees harmonically, write the RGB_inpainted
   python tools/propagate_reference.py --fixture [--ref-views 0] [--tol 0.05] --out DIR
   python tools/propagate_reference.py --datadir SCENE [--factor 4] --ref-views 0,30 [--ref-image A.png --ref-image B.png] --out DIR
   ... --depths field --checkpoint CKPT.tar      (the field's disparities, prepare.prepare_depths, instead of the dataset's rasters)
+  ... --inpaint exemplar [--fill exemplar]      (the reference images made here: prepare.inpaint_views, no network and no weights)
 
 --fixture uses tests/golden/scene1_small.npz (images, masks, 8-bit disparity rasters, poses); --datadir a SPIn-NeRF style scene
 with its RGB_inpainted/, label/ and Depth_inpainted/.  --ref-image replaces the image of a reference view, in the order of
---ref-views (a 2D inpainting made elsewhere); without it the scene's own image of that view is the reference.  --depths field
+--ref-views (a 2D inpainting made elsewhere); without it the scene's own image of that view is the reference, or with
+--inpaint exemplar that image with its mask filled by ops.exemplar_fill (texture copied from the rest of the image: plausible,
+not pixel-accurate).  --fill says what goes into the pixels no reference sees: the harmonic interpolant (the default), the
+exemplar fill (from pixels outside the view's mask), or nothing.  --depths field
 renders the disparities from a model instead (--checkpoint in the reference's .tar format; with --fixture and no checkpoint
 the 1,500-iteration recipe of tools/render_occupancy_ab.py::train_scene1 is trained first) and fills them inside the masks.
 
@@ -65,6 +69,9 @@ def main(argv=None):
     ap.add_argument('--ref-views', default='0', help='the inpainted views, comma separated (default 0)')
     ap.add_argument('--ref-image', action='append', default=[], metavar='PNG',
                     help='the inpainted image of a reference view, in the order of --ref-views; may be repeated')
+    ap.add_argument('--inpaint', choices=('none', 'exemplar'), default='none',
+                    help='make the reference images without a --ref-image here: exemplar = prepare.inpaint_views')
+    ap.add_argument('--fill', choices=('harmonic', 'exemplar', 'none'), default='harmonic', help='what fills the pixels no reference sees')
     ap.add_argument('--tol', type=float, default=0.05, help='relative depth tolerance of the visibility test')
     ap.add_argument('--depths', choices=('dataset', 'field'), default='dataset')
     ap.add_argument('--checkpoint', help='model for --depths field')
@@ -104,6 +111,9 @@ def main(argv=None):
         out, seconds['depths'] = timed(lambda: prepare.prepare_depths(te, hwf, torch.from_numpy(poses).to(dev), masks, near, far))
         disp = out['filled']
     ref_images = images[refs].copy()
+    if a.inpaint == 'exemplar' and len(a.ref_image) < len(refs):
+        made, seconds['inpaint'] = timed(lambda: prepare.inpaint_views(images, masks, refs[len(a.ref_image):]))
+        ref_images[len(a.ref_image):] = made.cpu().numpy()
     for k, path in enumerate(a.ref_image):
         png = load_llff._imread(path)[..., :3].astype(np.float32) / np.float32(255.)
         if png.shape != (H, W, 3):
@@ -111,9 +121,9 @@ def main(argv=None):
         ref_images[k] = png
     img_t, msk_t, pose_t = torch.from_numpy(images).to(dev), torch.from_numpy(masks).to(dev), torch.from_numpy(poses).to(dev)
     run = lambda tol, fill: prepare.propagate_reference(img_t, msk_t, disp, pose_t, hwf[2], refs, ref_images=ref_images, tol=tol, fill=fill)
-    _, seconds['warp_and_fill_first_call'] = timed(lambda: run(a.tol, True))
-    res, seconds['warp_and_fill'] = timed(lambda: run(a.tol, True))
-    _, seconds['warp'] = timed(lambda: run(a.tol, False))
+    _, seconds['warp_and_fill_first_call'] = timed(lambda: run(a.tol, a.fill))
+    res, seconds['warp_and_fill'] = timed(lambda: run(a.tol, a.fill))
+    _, seconds['warp'] = timed(lambda: run(a.tol, 'none'))
     got, source = res['images'].cpu().numpy(), res['source'].cpu().numpy()
     os.makedirs(a.out, exist_ok=True)
     clipped, seconds['write'] = timed(lambda: prepare.write_images(a.out, names, got))
@@ -129,20 +139,20 @@ def main(argv=None):
     in_mask, in_warped, baseline = per_view(got, masks), per_view(got, warped), per_view(base, masks)
     sweep = []
     for tol in SWEEP:
-        r = run(tol, True)
+        r = run(tol, a.fill)
         g, s = r['images'].cpu().numpy(), r['source'].cpu().numpy()
         sweep.append({'tol': tol, 'mean_coverage': float(np.mean(r['coverage'][others])) if others else None,
                       'min_coverage': float(np.min(r['coverage'][others])) if others else None,
                       'mean_rms_in_mask': mean(per_view(g, masks)), 'mean_rms_warped_pixels': mean(per_view(g, masks & (s >= 0)))})
     out = {'scene': 'tests/golden/scene1_small.npz' if a.fixture else a.datadir, 'frame': [H, W], 'views': N, 'ref_views': refs,
-           'ref_images': a.ref_image, 'depths': a.depths, 'tol': a.tol, 'mask_share_of_frame': float(masks.mean()),
+           'ref_images': a.ref_image, 'inpaint': a.inpaint, 'fill': a.fill, 'depths': a.depths, 'tol': a.tol, 'mask_share_of_frame': float(masks.mean()),
            'coverage_per_view': [float(c) for c in res['coverage']], 'holes_per_view': res['holes'].sum((1, 2)).cpu().tolist(),
            'rms_in_mask_per_view': in_mask, 'rms_warped_pixels_per_view': in_warped, 'rms_baseline_harmonic_fill_per_view': baseline,
            'mean_over_non_reference_views': {'coverage': float(np.mean(res['coverage'][others])) if others else None,
                                              'rms_in_mask': mean(in_mask), 'rms_warped_pixels': mean(in_warped),
                                              'rms_baseline_harmonic_fill': mean(baseline)},
            'note': 'RMS in 0..1 against the scene\'s own images (independent 2D inpaintings of every view) inside the masks',
-           'fill_iterations_max': int(res['info']['iterations'].max()), 'clipped_values': clipped, 'tol_sweep': sweep, 'seconds': seconds}
+           'fill_iterations_max': int(res['info']['iterations'].max()) if a.fill == 'harmonic' else None, 'clipped_values': clipped, 'tol_sweep': sweep, 'seconds': seconds}
     print(json.dumps(out, indent=1))
     json.dump(out, open(os.path.join(a.out, 'reference_propagation.json'), 'w'), indent=1)
     return 0
