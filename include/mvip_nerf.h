@@ -709,6 +709,16 @@ int mvip_mcubes_count(const float *grid, int nx, int ny, int nz, float iso, cons
 int mvip_mcubes_emit(const float *grid, int nx, int ny, int nz, float iso, float x0, float y0, float z0, float x1,
                      float y1, float z1, const void *tri_table, const void *flags, const int64_t *wg, int64_t n_verts,
                      int64_t n_tris, int *vid, float *verts, float *normals, int *faces, void *stream);
+/* mvip_mcubes_count_valid: mvip_mcubes_count restricted to observed cells (beyond the reference, which has no mesh export;
+ * mesh.fuse_depths).  valid [nx,ny,nz] bytes, non-zero = observed.  A cell is live iff its eight corners are valid; a cell
+ * that is not live gets cube index 0 (no triangles), and a point's owned edge keeps its crossing flag iff the values cross
+ * and at least one of the up to four cells sharing the edge is live: every vertex mvip_mcubes_emit then writes is
+ * referenced by a triangle, and every triangle's vertices exist.  The non-finite flag looks at valid points only (a point
+ * that is not valid may hold anything).  flags / wg / totals as mvip_mcubes_count, and mvip_mcubes_emit takes them
+ * unchanged; its normals are central differences of the grid and read the fill value of a point that is not valid within
+ * one lattice step of it.  valid all non-zero: the flags of mvip_mcubes_count, bit for bit.  A NULL operand is MVIP_EINVAL. */
+int mvip_mcubes_count_valid(const float *grid, const void *valid, int nx, int ny, int nz, float iso, const void *tri_table,
+                            void *flags, int64_t *wg, int64_t *totals, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Occupancy-grid empty-space skipping for no-grad renders (beyond the reference: it evaluates every
@@ -945,6 +955,27 @@ int mvip_exemplar_level(int64_t N, int H, int W, int patch, int levels, int leve
                         int rounds, int iters, unsigned seed, void *workspace, int *meta, const int *lists, void *stream);
 int mvip_exemplar_finish(const float *images, int64_t N, int H, int W, int patch, int levels, int rounds, int iters,
                          void *workspace, const int *meta, float *out, int *nnf, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * TSDF fusion of depth maps (beyond the reference, which renders depth images but has no mesh export and never fuses
+ * them; csrc/tsdf.hip, ops.tsdf_fuse, mesh.fuse_depths).  All operands DEVICE memory, dense:
+ *   disp [V,H,W] fp32 (disparity = 1 / planar depth, as prepare.render_disparities returns it), pose [V,3,4] row-major
+ *   camera-to-world [R | o] (the camera of mvip_warp_views: no half-pixel offset, looking down -z), mask [V,H,W] bytes
+ *   (0: ignore the pixel) or NULL; tsdf [nx,ny,nz] fp32 and count [nx,ny,nz] int32, z fastest; lattice point (i,j,k)
+ *   sits at x0 + i hx, ..., hx = (x1 - x0) / (nx - 1) in fp32 (the lattice of mvip_mcubes_emit).
+ * Per lattice point, over the views in ascending order: project into the view, take the NEAREST pixel (floor(u + .5),
+ * floor(w + .5)); the view counts iff the point is in front of the camera, the pixel is inside the image, its mask byte
+ * is set, its disparity d is finite and > 0 and sdf = 1/d - z >= -trunc (z: the point's planar depth); then it adds
+ * min(1, sdf / trunc).  tsdf = the mean over the counted views, or 1 when there are none; count = their number (the
+ * operation order is written out in csrc/tsdf.hip and tests/tsdf_numpy.py).
+ * One launch, one thread per lattice point, a pure gather: no atomics, every index bounded in the kernel, every element of
+ * both outputs written, a point's result independent of the others (bit-reproducible).  2 <= nx, ny, nz <= 768,
+ * 1 <= H, W <= 16384, V >= 0, the box finite and increasing, focal and trunc finite and > 0, else MVIP_EINVAL before
+ * anything is touched; a NULL output is MVIP_EINVAL, and so is a NULL disp or pose unless V == 0 (then tsdf = 1,
+ * count = 0 everywhere). */
+int mvip_tsdf_fuse(const float *disp, const float *pose, const void *mask, int V, int H, int W, float focal, int nx, int ny,
+                   int nz, float x0, float y0, float z0, float x1, float y1, float z1, float trunc, float *tsdf, int *count,
+                   void *stream);
 
 #ifdef __cplusplus
 }

@@ -165,6 +165,7 @@ _SIGNATURES = {
     'mvip_mcubes_count': (_int, [_c_f, _int, _int, _int, _flt, _c_f, _c_f, _c_f, _c_f, _c_f]),
     'mvip_mcubes_emit': (_int, [_c_f, _int, _int, _int, _flt, _flt, _flt, _flt, _flt, _flt, _flt, _c_f, _c_f, _c_f, _i64, _i64,
                                 _c_f, _c_f, _c_f, _c_f, _c_f]),
+    'mvip_mcubes_count_valid': (_int, [_c_f, _c_f, _int, _int, _int, _flt, _c_f, _c_f, _c_f, _c_f, _c_f]),
     'mvip_occupancy_build': (_int, [_c_f, _int, _int, _int, _int, _flt, _c_f, _c_f]),
     'mvip_occupancy_dilate': (_int, [_c_f, _int, _int, _int, _c_f, _c_f]),
     'mvip_occupancy_groups': (_i64, [_i64, _int]),
@@ -201,6 +202,8 @@ _SIGNATURES = {
     'mvip_exemplar_lists': (_int, [_i64, _int, _int, _int, _int, _c_f, _c_f, _c_f, _i64, _c_f]),
     'mvip_exemplar_level': (_int, [_i64, _int, _int, _int, _int, _int, _i64, _i64, _int, _int, ctypes.c_uint, _c_f, _c_f, _c_f, _c_f]),
     'mvip_exemplar_finish': (_int, [_c_f, _i64, _int, _int, _int, _int, _int, _int, _c_f, _c_f, _c_f, _c_f, _c_f]),
+    'mvip_tsdf_fuse': (_int, [_c_f, _c_f, _c_f, _int, _int, _int, _flt, _int, _int, _int, _flt, _flt, _flt, _flt, _flt, _flt, _flt,
+                              _c_f, _c_f, _c_f]),
 }
 
 # every symbol include/mvip_nerf.h declares; tests check the built library exports all of them

@@ -7,7 +7,9 @@
 //   1. mc_classify:  per point the crossing flags of its three owned lattice edges (+x, +y, +z: 0..3 vertices) and, for a
 //      cell origin, the 8-bit cube index; one uint16 per point = cube | flags << 8.  Workgroup totals of vertices and
 //      triangles (the triangle count of each cube index, read off the table, staged in LDS); a non-finite value raises a
-//      device flag with a plain vector store.
+//      device flag with a plain vector store.  With a validity lattice (mvip_mcubes_count_valid) only live cells and the
+//      edges around them are classified; the later passes read nothing but the flags, so they are shared.  Normals stay
+//      central differences of the grid: within one lattice step of a point that is not valid they read its fill value.
 //   2. scan:         one workgroup: exclusive int64 scan of the workgroup totals in place, and the two grand totals.
 //      The host reads the totals once, to allocate the outputs (the only synchronisation).
 //   3. mc_vertices:  per point its first vertex id (int32), and per crossing edge the position and the normal: the
@@ -37,7 +39,14 @@ __device__ __forceinline__ int tri_count(const signed char *tab, int cube) {
     return c;
 }
 
-__global__ __launch_bounds__(BLOCK) void mc_classify_kernel(const float *__restrict__ v, int nx, int ny, int nz, float iso,
+// MASKED (mvip_mcubes_count_valid): `valid` [nx, ny, nz] bytes, non-zero = observed.  A cell is live iff its eight corners are
+// valid; a cell that is not live gets cube index 0, and an owned edge keeps its crossing flag only if one of the up to four cells
+// around it is live -- so every vertex is referenced by a triangle and every triangle's vertices exist.  Liveness is read off the
+// corners directly (the 27 bytes around the point, shared by its seven cells; every index bounded, a point outside the grid
+// counts as not valid); the non-finite check applies to valid points only.
+template <bool MASKED>
+__global__ __launch_bounds__(BLOCK) void mc_classify_kernel(const float *__restrict__ v, const unsigned char *__restrict__ valid,
+                                                           int nx, int ny, int nz, float iso,
                                                            const signed char *__restrict__ table,
                                                            unsigned short *__restrict__ flags,
                                                            long long *__restrict__ wg_sums, unsigned *__restrict__ nonfinite) {
@@ -55,18 +64,36 @@ __global__ __launch_bounds__(BLOCK) void mc_classify_kernel(const float *__restr
             int i, j, k;
             linear_ijk(n, ny, nz, i, j, k);
             const float v0 = v[n];
-            if (!finite(v0)) *nonfinite = 1u;      // NaN or +-inf
+            if (!finite(v0) && (!MASKED || valid[n] != 0)) *nonfinite = 1u;      // NaN or +-inf
             const bool xi = i + 1 < nx, yi = j + 1 < ny, zi = k + 1 < nz;
             const unsigned c0 = v0 >= iso;
             const unsigned c1 = xi ? (v[n + sx] >= iso) : c0;
             const unsigned c2 = yi ? (v[n + sy] >= iso) : c0;
             const unsigned c4 = zi ? (v[n + 1] >= iso) : c0;
-            const unsigned mask = (c0 ^ c1) | ((c0 ^ c2) << 1) | ((c0 ^ c4) << 2);
+            unsigned mask = (c0 ^ c1) | ((c0 ^ c2) << 1) | ((c0 ^ c4) << 2);
             unsigned cube = 0;
             if (xi && yi && zi) {
                 const unsigned c3 = v[n + sx + sy] >= iso, c5 = v[n + sx + 1] >= iso;
                 const unsigned c6 = v[n + sy + 1] >= iso, c7 = v[n + sx + sy + 1] >= iso;
                 cube = c0 | (c1 << 1) | (c2 << 2) | (c3 << 3) | (c4 << 4) | (c5 << 5) | (c6 << 6) | (c7 << 7);
+            }
+            if constexpr (MASKED) {
+                // ok(dx, dy, dz): the point at that offset (-1..1 each) exists and is valid
+                auto ok = [&](int dx, int dy, int dz) -> unsigned {
+                    const int a = i + dx, b = j + dy, c = k + dz;
+                    if (a < 0 || a >= nx || b < 0 || b >= ny || c < 0 || c >= nz) return 0u;
+                    return valid[n + dx * sx + dy * sy + dz] != 0 ? 1u : 0u;
+                };
+                // live(a, b, c): the cell whose origin is at offset (a, b, c) (-1 or 0 each) has eight valid corners
+                auto live = [&](int a, int b, int c) -> unsigned {
+                    return ok(a, b, c) & ok(a + 1, b, c) & ok(a, b + 1, c) & ok(a + 1, b + 1, c) & ok(a, b, c + 1) &
+                           ok(a + 1, b, c + 1) & ok(a, b + 1, c + 1) & ok(a + 1, b + 1, c + 1);
+                };
+                const unsigned l000 = live(0, 0, 0), l0m0 = live(0, -1, 0), l00m = live(0, 0, -1), l0mm = live(0, -1, -1);
+                const unsigned lm00 = live(-1, 0, 0), lm0m = live(-1, 0, -1), lmm0 = live(-1, -1, 0);
+                const unsigned ex = l000 | l0m0 | l00m | l0mm, ey = l000 | lm00 | l00m | lm0m, ez = l000 | lm00 | l0m0 | lmm0;
+                mask &= ex | (ey << 1) | (ez << 2);
+                cube = l000 ? cube : 0u;
             }
             flags[n] = (unsigned short)(cube | (mask << 8));
             nv = __popc(mask);
@@ -201,8 +228,24 @@ extern "C" int mvip_mcubes_count(const float *grid, int nx, int ny, int nz, floa
     hipStream_t s = as_stream(stream);
     const int64_t G = mvip_mcubes_groups(nx, ny, nz);
     zero_words(totals + 2, 2, s);                               // totals[2]: the non-finite flag
-    hipLaunchKernelGGL(mc::mc_classify_kernel, dim3((unsigned)G), dim3(mc::BLOCK), 0, s, grid, nx, ny, nz, iso,
-                       (const signed char *)tri_table, (unsigned short *)flags, (long long *)wg, (unsigned *)(totals + 2));
+    hipLaunchKernelGGL(mc::mc_classify_kernel<false>, dim3((unsigned)G), dim3(mc::BLOCK), 0, s, grid,
+                       (const unsigned char *)nullptr, nx, ny, nz, iso, (const signed char *)tri_table, (unsigned short *)flags,
+                       (long long *)wg, (unsigned *)(totals + 2));
+    hipLaunchKernelGGL((compact::scan_kernel<long long, 2>), dim3(1), dim3(compact::SCAN_BLOCK), 0, s, (long long *)wg,
+                       (int)G, (long long *)totals);
+    return check_launch();
+}
+
+extern "C" int mvip_mcubes_count_valid(const float *grid, const void *valid, int nx, int ny, int nz, float iso,
+                                       const void *tri_table, void *flags, int64_t *wg, int64_t *totals, void *stream) {
+    if (!mc_shape_ok(nx, ny, nz) || !(iso > 0.f) || !finite(iso)) return MVIP_EINVAL;
+    if (!grid || !valid || !tri_table || !flags || !wg || !totals) return MVIP_EINVAL;
+    hipStream_t s = as_stream(stream);
+    const int64_t G = mvip_mcubes_groups(nx, ny, nz);
+    zero_words(totals + 2, 2, s);                               // totals[2]: the non-finite flag
+    hipLaunchKernelGGL(mc::mc_classify_kernel<true>, dim3((unsigned)G), dim3(mc::BLOCK), 0, s, grid,
+                       (const unsigned char *)valid, nx, ny, nz, iso, (const signed char *)tri_table, (unsigned short *)flags,
+                       (long long *)wg, (unsigned *)(totals + 2));
     hipLaunchKernelGGL((compact::scan_kernel<long long, 2>), dim3(1), dim3(compact::SCAN_BLOCK), 0, s, (long long *)wg,
                        (int)G, (long long *)totals);
     return check_launch();

@@ -3,7 +3,8 @@
 density_grid() samples sigma on a dense grid with the model's own no-grad query path (`render_kwargs['network_query_fn']`:
 the fused 8x256 MLP kernel for create_nerf, the fused hash-grid kernel for create_nerf_tcnn); marching_cubes() turns it into
 an indexed, crack-free triangle mesh with the HIP passes of csrc/mcubes.hip; extract_mesh() does both and colours the
-vertices; save_ply() writes the result.  There is no CPU path: grids and meshes live on the device until save_ply.
+vertices; save_ply() writes the result.  fuse_depths() / extract_mesh_tsdf() mesh what the renderer sees instead: the
+rendered depth maps of the views fused into a truncated signed distance field (csrc/tsdf.hip), zero level set.  There is no CPU path: grids and meshes live on the device until save_ply.
 
 Conventions (shared with csrc/mcubes.hip and the test restatement tests/mc_numpy.py): grid [nx, ny, nz], z fastest; point
 (i, j, k) sits at bmin + (i, j, k) * (bmax - bmin) / (n - 1), in fp32 arithmetic; a corner is inside iff sigma >= threshold
@@ -322,10 +323,14 @@ def _check_axes(shape):
         raise ValueError(f'grid {tuple(shape)}: three axes of 2..{MAX_POINTS_PER_AXIS} points each')
 
 
-def marching_cubes(grid, threshold, bound_min, bound_max):
+def marching_cubes(grid, threshold, bound_min, bound_max, valid=None):
     """grid [nx, ny, nz] fp32 device tensor -> (verts [V, 3] f32, faces [F, 3] int32, normals [V, 3] f32), all on the
     grid's device.  An empty surface gives (0, 3) tensors.  Raises ValueError for a non-finite grid, threshold <= 0,
-    bound_min >= bound_max on an axis or an axis outside 2..768 points."""
+    bound_min >= bound_max on an axis or an axis outside 2..768 points.
+    valid (None: every point, the path without a validity lattice): [nx, ny, nz] bool, True = observed.  Only cells whose
+    eight corners are valid give triangles and only the edges around such cells vertices, so no surface appears where
+    observed space meets unobserved space; a point that is not valid may hold anything, NaN included.  Normals stay
+    central differences of the grid: within one lattice step of a point that is not valid they read its fill value."""
     if not torch.is_tensor(grid):
         raise ValueError('grid must be a torch tensor on the GPU')
     _check_axes(grid.shape)
@@ -333,7 +338,7 @@ def marching_cubes(grid, threshold, bound_min, bound_max):
     if not (threshold > 0 and math.isfinite(threshold)):
         raise ValueError(f'threshold must be finite and > 0, got {threshold}')
     lo, hi = _bounds(bound_min, bound_max)
-    return ops.marching_cubes(grid, threshold, lo, hi, device_table(grid.device))
+    return ops.marching_cubes(grid, threshold, lo, hi, device_table(grid.device), valid=valid)
 
 
 def grid_axes(bound_min, bound_max, resolution, device):
@@ -442,6 +447,47 @@ def extract_mesh(render_kwargs, bound_min, bound_max, resolution=256, threshold=
     verts, faces, normals = marching_cubes(grid, threshold, bound_min, bound_max)
     rgb = vertex_colors(render_kwargs, verts, normals, network, chunk) if colors else None
     return Mesh(verts, faces, normals, rgb)
+
+
+def fuse_depths(disp, poses, focal, bound_min, bound_max, resolution=256, trunc=None, masks=None, largest=None,
+                min_points=None):
+    """Mesh(verts, faces, normals, None) of the surface the depth maps see: ops.tsdf_fuse (csrc/tsdf.hip) fuses disp
+    [V, H, W] (disparity = 1 / planar depth, as prepare.render_disparities returns it) of the cameras poses [V, 3, 4] into
+    a truncated signed distance field on the lattice of the box, and marching cubes extracts its zero level set over the
+    observed cells.  No threshold to choose: the iso value is 0.  trunc=None means four times the largest lattice step;
+    masks [V, H, W] bool: False = ignore the pixel.
+
+    The lattice handed to marching cubes is g = 1 - tsdf at threshold 1 (inside <=> g >= 1 <=> tsdf <= 0, the "threshold > 0,
+    inside is >=" contract), with 0 at the points no view observed and valid = count > 0.  largest / min_points:
+    remove_floaters(g, 1.0, ...) first (connectivity 6).  Normals point toward the cameras; within one lattice step of an
+    unobserved point they read the fill value 0."""
+    lo, hi = _bounds(bound_min, bound_max)
+    res = (int(resolution),) * 3 if np.isscalar(resolution) else tuple(int(n) for n in resolution)
+    _check_axes(res)
+    if trunc is None:
+        trunc = 4.0 * max(float((hi[a] - lo[a]) / np.float32(res[a] - 1)) for a in range(3))
+    tsdf, count = ops.tsdf_fuse(disp, poses, focal, lo, hi, res, trunc, masks=masks)
+    valid = count > 0
+    g = torch.where(valid, 1.0 - tsdf, torch.zeros((), device=tsdf.device, dtype=tsdf.dtype))
+    if largest is not None or min_points is not None:
+        g = remove_floaters(g, 1.0, largest, min_points, connectivity=6)
+    verts, faces, normals = marching_cubes(g, 1.0, lo, hi, valid=valid)
+    return Mesh(verts, faces, normals, None)
+
+
+def extract_mesh_tsdf(render_kwargs, hwf, poses, near, far, bound_min, bound_max, resolution=256, trunc=None, colors=True,
+                      network='fine', chunk=1 << 15, largest=None, min_points=None, masks=None):
+    """Mesh of what the renderer sees rather than of what the network stores: prepare.render_disparities of every pose
+    [V, 3, 4] (hwf = (H, W, focal); `chunk` rays at a time), fuse_depths() of those maps, colours from vertex_colors()
+    (uint8 [V, 3]) or None with colors=False.  Compositing has integrated the fog along each ray away and the average over
+    the views removes view-dependent floaters, so no sigma threshold is chosen.  Refuses NDC models (ValueError)."""
+    from . import prepare
+    _network(render_kwargs, network)
+    disp = prepare.render_disparities(render_kwargs, hwf, poses, near, far, chunk=chunk)
+    poses = torch.as_tensor(poses).to(device=disp.device, dtype=torch.float32)[:, :3, :4].contiguous()
+    m = fuse_depths(disp, poses, float(hwf[2]), bound_min, bound_max, resolution, trunc, masks, largest, min_points)
+    rgb = vertex_colors(render_kwargs, m.verts, m.normals, network) if colors else None
+    return Mesh(m.verts, m.faces, m.normals, rgb)
 
 
 def frustum_bounds(poses, hwf, near, far):

@@ -1775,24 +1775,38 @@ def ddim_cfg_step(eps, x, scal, unet_in=None, t_out=None):
 
 # marching cubes (beyond the reference: mesh export, mvip_nerf_amd/mesh.py) -----------------------------
 
-def marching_cubes(grid, iso, bound_min, bound_max, tri_table):
+def marching_cubes(grid, iso, bound_min, bound_max, tri_table, valid=None):
     """grid [nx, ny, nz] fp32 on the device -> (verts [V, 3] f32, faces [F, 3] int32, normals [V, 3] f32), csrc/mcubes.hip.
     tri_table: the 256 x 16 int8 device table of mesh.py.  Reads back the two totals and the non-finite flag once (the
-    only synchronisation); raises ValueError for a non-finite grid, MvipError for more than 2^31 - 1 triangles."""
+    only synchronisation); raises ValueError for a non-finite grid, MvipError for more than 2^31 - 1 triangles.
+    valid (None: every point): [nx, ny, nz] bool or uint8 on the grid's device, non-zero = observed; only cells whose eight
+    corners are valid give triangles, only the edges around them vertices, and a point that is not valid may hold anything
+    (mvip_mcubes_count_valid)."""
     g = _f32c(grid)
     nx, ny, nz = (int(s) for s in g.shape)
     dev = g.device
+    if valid is not None:
+        if not torch.is_tensor(valid) or valid.dtype not in (torch.bool, torch.uint8) or tuple(valid.shape) != tuple(g.shape):
+            got = f'{tuple(valid.shape)} {valid.dtype}' if torch.is_tensor(valid) else type(valid).__name__
+            raise ValueError(f'marching_cubes: valid must be a bool or uint8 tensor {tuple(g.shape)}, got {got}')
+        if valid.device != dev:
+            raise ValueError(f'marching_cubes: valid on {valid.device}, the grid on {dev}')
+        valid = valid.detach().contiguous()
     G = _lib.load().mvip_mcubes_groups(nx, ny, nz)
     if G < 0:
         raise _lib.MvipError(f'marching_cubes: grid {tuple(g.shape)} outside 2..768 points per axis')
     flags = torch.empty(nx * ny * nz, device=dev, dtype=torch.int16)
     wg = torch.empty((G, 2), device=dev, dtype=torch.int64)
     totals = torch.empty(3, device=dev, dtype=torch.int64)
-    call('mvip_mcubes_count', ptr(g), nx, ny, nz, float(iso), ptr(tri_table, torch.int8), ptr(flags, torch.int16),
-         ptr(wg, torch.int64), ptr(totals, torch.int64), stream())
+    if valid is None:
+        call('mvip_mcubes_count', ptr(g), nx, ny, nz, float(iso), ptr(tri_table, torch.int8), ptr(flags, torch.int16),
+             ptr(wg, torch.int64), ptr(totals, torch.int64), stream())
+    else:
+        call('mvip_mcubes_count_valid', ptr(g), ptr(valid, valid.dtype), nx, ny, nz, float(iso), ptr(tri_table, torch.int8),
+             ptr(flags, torch.int16), ptr(wg, torch.int64), ptr(totals, torch.int64), stream())
     n_verts, n_tris, nonfinite = (int(x) for x in totals.cpu())
     if nonfinite:
-        raise ValueError('marching_cubes: the grid holds a non-finite value')
+        raise ValueError('marching_cubes: the grid holds a non-finite value' + (' at a valid point' if valid is not None else ''))
     if n_tris > 2 ** 31 - 1:
         raise _lib.MvipError(f'marching_cubes: {n_tris} triangles exceed int32 face indices')
     verts = torch.empty((n_verts, 3), device=dev, dtype=_F32)
@@ -2228,6 +2242,55 @@ def warp_views(tgt_disp, tgt_pose, tgt_mask, src_rgb, src_disp, src_pose, focal,
     call('mvip_warp_views', ptr(d), ptr(tp), ptr(m, torch.bool), N, H, W, ptr(sc), ptr(sd), ptr(sp), S, ptr(order.detach(), _I32),
          focal, tol, ptr(rgb), ptr(index, _I32), ptr(resid), stream())
     return rgb, index, resid
+
+
+# TSDF fusion of depth maps (beyond the reference, which has no mesh export; csrc/tsdf.hip, mesh.fuse_depths) -----------------------
+
+def tsdf_fuse(disp, poses, focal, bound_min, bound_max, resolution, trunc, masks=None):
+    """Fuse V disparity maps into a truncated signed distance field on a lattice (the definition is csrc/tsdf.hip's and
+    tests/tsdf_numpy.py's).  disp [V, H, W] fp32 (1 / planar depth, as prepare.render_disparities returns it), poses [V, 3, 4]
+    camera-to-world, masks [V, H, W] bool (False: ignore the pixel) or None; bound_min / bound_max: three coordinates each;
+    resolution: an int or three point counts (2..768 each); trunc: the truncation distance, finite and > 0.  Returns
+    (tsdf [nx, ny, nz] fp32 in [-1, 1]: the mean over the views that see the point of min(1, (depth - z) / trunc), 1 where
+    there is none; count [nx, ny, nz] int32: those views).  A view sees a point iff it projects onto a pixel (the nearest
+    one) with a finite disparity > 0 and lies no more than trunc behind that pixel's surface.  One launch.  Detached."""
+    import math
+    import numpy as np
+    what = 'tsdf_fuse'
+    d = _image_batch(what, disp, _F32, 'disp')
+    p = _pose_batch(what, poses, 'poses')
+    V, H, W = d.shape
+    if p.shape[0] != V:
+        raise ValueError(f'{what}: disp {tuple(d.shape)}, poses {tuple(p.shape)}: one V expected')
+    if H < 1 or W < 1:
+        raise ValueError(f'{what}: images of at least 1 x 1 expected, got {H} x {W}')
+    tensors = [d, p]
+    m = None
+    if masks is not None:
+        m = _image_batch(what, masks, torch.bool, 'masks')
+        if tuple(m.shape) != (V, H, W):
+            raise ValueError(f'{what}: masks {tuple(m.shape)} for disp {tuple(d.shape)}')
+        tensors.append(m)
+    _on_gpu(what, *tensors)
+    if any(t.device != d.device for t in tensors):
+        raise ValueError(f'{what}: tensors on one device expected, got {sorted({str(t.device) for t in tensors})}')
+    if not all(t.is_contiguous() for t in tensors):
+        raise ValueError(f'{what}: every operand must be contiguous')
+    lo = [float(np.float32(v)) for v in bound_min]
+    hi = [float(np.float32(v)) for v in bound_max]
+    if len(lo) != 3 or len(hi) != 3 or not all(math.isfinite(a) and math.isfinite(b) and a < b for a, b in zip(lo, hi)):
+        raise ValueError(f'{what}: bound_min {lo} must be finite and below bound_max {hi} on every axis')
+    res = (int(resolution),) * 3 if np.isscalar(resolution) else tuple(int(n) for n in resolution)
+    if len(res) != 3 or not all(2 <= n <= MAX_COMPONENT_AXIS for n in res):
+        raise ValueError(f'{what}: resolution {res}: three axes of 2..{MAX_COMPONENT_AXIS} points each')
+    focal, trunc = float(focal), float(trunc)
+    if not (0.0 < focal < float('inf') and 0.0 < trunc < float('inf')):
+        raise ValueError(f'{what}: focal {focal} and trunc {trunc} must be finite and > 0')
+    tsdf = torch.empty(res, device=d.device, dtype=_F32)
+    count = torch.empty(res, device=d.device, dtype=_I32)
+    call('mvip_tsdf_fuse', ptr(d), ptr(p), ptr(m, torch.bool), V, H, W, focal, res[0], res[1], res[2], lo[0], lo[1], lo[2],
+         hi[0], hi[1], hi[2], trunc, ptr(tsdf), ptr(count, _I32), stream())
+    return tsdf, count
 
 
 # structural similarity with its gradient (beyond the reference, whose evaluation.py takes its metrics from pyiqa; csrc/ssim.hip) --

@@ -5,10 +5,19 @@ binary PLY (mvip_nerf_amd/mesh.py).  Prints sigma percentiles of the grid (to ch
   python tools/extract_mesh.py CKPT.tar --out mesh.ply [--model mlp|tcnn] [--bound-min x y z --bound-max x y z]
          [--resolution 256] [--threshold 10] [--network fine|coarse] [--precision fp32|split] [--no-colors]
          [--keep-largest K] [--min-component N]
+  python tools/extract_mesh.py --tsdf --fixture [--iters 1500] --out mesh.ply [--trunc T] [--view-step S] ...
+  python tools/extract_mesh.py --tsdf CKPT.tar --datadir SCENE [--factor 4] --out mesh.ply [--trunc T] [--view-step S] ...
 
 --keep-largest K keeps the K largest connected components of the inside lattice points, --min-component N those of at
 least N points (mesh.remove_floaters, connectivity 6; both: a component must meet both); the counts before and after are
 printed.
+
+--tsdf meshes what the renderer sees instead of thresholding sigma (mesh.fuse_depths): the disparity of every view (every
+S-th with --view-step S) is rendered and fused into a truncated signed distance field whose zero level set is extracted
+over the observed cells; --threshold is not used.  It needs the cameras, taken the way tools/prepare_depths.py takes them:
+--fixture trains the scene-1 fixture, a checkpoint comes with --datadir / --factor.  --trunc: the truncation distance
+(default: four times the largest lattice step).  Without --bound-min / --bound-max the box is the cameras' frustum box
+(mesh.frustum_bounds).  Prints the observed share of the lattice and each stage's time.
 """
 import argparse
 import os
@@ -47,13 +56,63 @@ def load_model(path, model, device):
     return kw, int(ckpt.get('global_step', 0))
 
 
+def _timed(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = fn()
+    torch.cuda.synchronize()
+    return out, time.perf_counter() - t0
+
+
+def main_tsdf(ap, a, res, dev):
+    """--tsdf: render the views' disparities, fuse them, extract the zero level set over the observed cells."""
+    from mvip_nerf_amd import prepare
+    from tools import propagate_masks as P
+    if a.fixture == bool(a.ckpt) or bool(a.ckpt) != bool(a.datadir) or a.view_step < 1:
+        ap.error('--tsdf: either --fixture, or a checkpoint with --datadir; --view-step >= 1')
+    if a.model != 'mlp':
+        ap.error('--tsdf: the cameras are taken with the mlp model only')
+    (te, hwf, poses, _, _, names, near, far, source), t_model = _timed(
+        lambda: P.fixture_scene(dev, a.iters) if a.fixture else P.checkpoint_scene(dev, a.ckpt, a.datadir, a.factor))
+    for net in (te['network_fn'], te.get('network_fine')):
+        if net is not None:
+            net.inference_precision = 1 if a.precision == 'split' else 0
+    poses = poses[::a.view_step, :3, :4].contiguous().float()
+    if (a.bound_min is None) != (a.bound_max is None):
+        ap.error('--bound-min and --bound-max come together')
+    lo, hi = (a.bound_min, a.bound_max) if a.bound_min is not None else mesh.frustum_bounds(poses, hwf, near, far)
+    disp, t_render = _timed(lambda: prepare.render_disparities(te, hwf, poses, near, far))
+    lo32, hi32 = mesh._bounds(lo, hi)
+    res3 = (res,) * 3 if np.isscalar(res) else tuple(res)
+    trunc = a.trunc if a.trunc is not None else 4.0 * max(float((hi32[k] - lo32[k]) / np.float32(res3[k] - 1)) for k in range(3))
+    (tsdf, count), t_fuse = _timed(lambda: ops.tsdf_fuse(disp, poses, hwf[2], lo32, hi32, res3, trunc))
+    valid = count > 0
+    g = torch.where(valid, 1.0 - tsdf, torch.zeros((), device=dev))
+    print(f'{source}: {poses.shape[0]} views of {hwf[0]} x {hwf[1]}, lattice {tuple(tsdf.shape)} in {[round(float(v), 4) for v in lo32]} .. '
+          f'{[round(float(v), 4) for v in hi32]}, trunc {trunc:.4g}')
+    print(f'observed share of the lattice {float(valid.float().mean()):.4f}  (inside: {float((valid & (tsdf <= 0)).float().mean()):.4f})')
+    t_cc = 0.0
+    if a.keep_largest is not None or a.min_component is not None:
+        n_before = int(ops.grid_components(ops.grid_pack(g, 1.0), g.shape)[1].shape[0])
+        g, t_cc = _timed(lambda: mesh.remove_floaters(g, 1.0, a.keep_largest, a.min_component))
+        n_after = int(ops.grid_components(ops.grid_pack(g, 1.0), g.shape)[1].shape[0])
+        print(f'components of the inside points: {n_before} -> {n_after} kept')
+    (verts, faces, normals), t_mc = _timed(lambda: mesh.marching_cubes(g, 1.0, lo32, hi32, valid=valid))
+    colors, t_col = (None, 0.0) if a.no_colors else _timed(lambda: mesh.vertex_colors(te, verts, normals, a.network))
+    _, t_ply = _timed(lambda: mesh.save_ply(a.out, mesh.Mesh(verts, faces, normals, colors)))
+    print(f'tsdf zero level set: {verts.shape[0]} vertices, {faces.shape[0]} triangles -> {a.out}')
+    print(f'time  model {t_model * 1e3:.1f} ms  render {t_render * 1e3:.1f} ms  fusion {t_fuse * 1e3:.1f} ms  components {t_cc * 1e3:.1f} ms  '
+          f'marching cubes {t_mc * 1e3:.1f} ms  colours {t_col * 1e3:.1f} ms  write {t_ply * 1e3:.1f} ms')
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
-    ap.add_argument('ckpt')
+    ap.add_argument('ckpt', nargs='?')
     ap.add_argument('--out', required=True)
     ap.add_argument('--model', choices=('mlp', 'tcnn'), default='mlp')
-    ap.add_argument('--bound-min', type=float, nargs=3, default=(-1.0, -1.0, -1.0))
-    ap.add_argument('--bound-max', type=float, nargs=3, default=(1.0, 1.0, 1.0))
+    ap.add_argument('--bound-min', type=float, nargs=3, default=None, help='default -1 -1 -1; with --tsdf the frustum box')
+    ap.add_argument('--bound-max', type=float, nargs=3, default=None, help='default 1 1 1; with --tsdf the frustum box')
     ap.add_argument('--resolution', type=int, nargs='+', default=[256], help='one count, or three')
     ap.add_argument('--threshold', type=float, default=10.0)
     ap.add_argument('--network', choices=('fine', 'coarse'), default='fine')
@@ -61,9 +120,22 @@ def main(argv=None):
     ap.add_argument('--no-colors', action='store_true')
     ap.add_argument('--keep-largest', type=int, default=None, metavar='K', help='keep the K largest components')
     ap.add_argument('--min-component', type=int, default=None, metavar='N', help='drop components below N lattice points')
+    ap.add_argument('--tsdf', action='store_true', help='fuse rendered depth maps instead of thresholding sigma')
+    ap.add_argument('--fixture', action='store_true', help='--tsdf: train the scene-1 fixture and use its cameras')
+    ap.add_argument('--iters', type=int, default=1500, help='training iterations of --fixture')
+    ap.add_argument('--datadir', help='--tsdf with a checkpoint: the scene whose cameras are rendered')
+    ap.add_argument('--factor', type=int, default=4)
+    ap.add_argument('--trunc', type=float, default=None, help='--tsdf: truncation distance (default: 4 lattice steps)')
+    ap.add_argument('--view-step', type=int, default=1, metavar='S', help='--tsdf: fuse every S-th view')
     a = ap.parse_args(argv)
     res = a.resolution[0] if len(a.resolution) == 1 else tuple(a.resolution)
     dev = torch.device('cuda', 0)
+    if a.tsdf:
+        return main_tsdf(ap, a, res, dev)
+    if a.fixture or a.datadir or a.ckpt is None:
+        ap.error('a checkpoint is required; --fixture / --datadir belong to --tsdf')
+    a.bound_min = (-1.0, -1.0, -1.0) if a.bound_min is None else a.bound_min
+    a.bound_max = (1.0, 1.0, 1.0) if a.bound_max is None else a.bound_max
     kw, step = load_model(a.ckpt, a.model, dev)
     if a.model == 'mlp':
         for net in (kw['network_fn'], kw['network_fine']):
