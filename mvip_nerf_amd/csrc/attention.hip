@@ -16,7 +16,7 @@
 //
 // Operand formats (all produced by small packers so every LDS fill is a 1-KiB DMA piece and every fragment
 // one ds_read_b128):
-//   Q, K : "split planes" [N][chunks][kg 2][hl 2][tokens][8 halves] (the format of csrc/conv3x3.hip): plane
+//   Q, K : "split planes" [N][chunks][kg 2][hl 2][tokens][8 halves] (the format of csrc/f16x3_operand.h): plane
 //          (kg, hl) of 16-channel chunk ck holds channels ck*16 + kg*8 + 0..7 of every token as the hi / lo
 //          fp16 term; head h owns chunks h*NCH .. h*NCH + NCH - 1 (head dim padded to a multiple of 16 with
 //          zero channels: 40 -> 48).  Values are pre-scaled by a power of two (scale2 = {s, 1/s}).
@@ -28,20 +28,11 @@
 // K / V tiles of KT keys are staged through LDS by DMA (global_load_lds), double-buffered, one barrier per
 // tile; 124 registers and 28 KB of LDS for the 40-channel heads (32-key tiles) so that four waves share a SIMD and
 // one wave's softmax (VALU) runs under the others' MFMAs.
-#include "common.h"
+#include "f16x3_operand.h"
 #include "plane_sink.h"
 
 namespace mvip {
 namespace attn {
-
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ void glds16b(const void *src_lane, void *dst_wave) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src_lane,
-                                     (__attribute__((address_space(3))) void *)dst_wave, 16, 0, 0);
-}
 
 struct AttnArgs {
     const char *qs, *ks, *vp;
@@ -257,25 +248,18 @@ attn_pack_v_kernel(const float *__restrict__ v, int heads, int DP, int Lk, int L
     const int64_t n = r / heads;
     const int d = dt * 32 + (lane & 31), hh = lane >> 5;
     const float s = scale2[0];
-    unsigned hi[4], lo[4];
+    float x[8];
 #pragma unroll
-    for (int jp = 0; jp < 4; ++jp) {
-        float x[2];
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-            const int j = 2 * jp + e;
-            const int key = 16 * s16 + 8 * (j >> 2) + 4 * hh + (j & 3);
-            x[e] = (d < DP && key < Lk) ? v[n * sn + (int64_t)(head * DP + d) * sr + (int64_t)key * sk] * s : 0.f;
-        }
-        h16x2 a, b;
-        a.x = (_Float16)x[0]; a.y = (_Float16)x[1];
-        b.x = (_Float16)(x[0] - (float)a.x); b.y = (_Float16)(x[1] - (float)a.y);
-        hi[jp] = __builtin_bit_cast(unsigned, a); lo[jp] = __builtin_bit_cast(unsigned, b);
+    for (int j = 0; j < 8; ++j) {
+        const int key = 16 * s16 + 8 * (j >> 2) + 4 * hh + (j & 3);
+        x[j] = (d < DP && key < Lk) ? v[n * sn + (int64_t)(head * DP + d) * sr + (int64_t)key * sk] * s : 0.f;
     }
+    uint4 hi, lo;
+    split8(x, hi, lo);
     // [n][head][dt][s16][hl][lane]
     const int64_t base = ((((n * heads + head) * DT + dt) * (LkP / 16) + s16) * 2) * 64 + lane;
-    out[base] = make_uint4(hi[0], hi[1], hi[2], hi[3]);
-    if (prec != 1) out[base + 64] = make_uint4(lo[0], lo[1], lo[2], lo[3]);
+    out[base] = hi;
+    if (prec != 1) out[base + 64] = lo;
 }
 
 // ---- absolute maxima of several equally long sections at once -> one power-of-two scale per section ----
@@ -285,7 +269,7 @@ absmax_sections_kernel(const float *__restrict__ x, int64_t outer, int sections,
                        float *__restrict__ scale2) {
     const int s = blockIdx.y;
     float m = 0.f;
-    auto take = [&](float v) { v = fabsf(v); m = (v == v && v < 3.0e38f) ? fmaxf(m, v) : m; };
+    auto take = [&](float v) { m = absmax_take(m, v); };
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t n4 = len >> 2;
@@ -299,13 +283,9 @@ absmax_sections_kernel(const float *__restrict__ x, int64_t outer, int sections,
             for (int64_t i = tid; i < len; i += stride) take(xs[i]);
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    __shared__ float wm[4];
-    if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
-    __syncthreads();
+    m = block256_max(m);
     if (threadIdx.x == 0) {
-        atomicMax(bits + s, __float_as_uint(fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]))));
+        atomicMax(bits + s, __float_as_uint(m));
         // the last workgroup of the launch (ticket in bits[63]) turns every section's maximum into its scale and leaves
         // the scratch words zero for the next user: no separate scale launch
         __threadfence();
@@ -313,39 +293,20 @@ absmax_sections_kernel(const float *__restrict__ x, int64_t outer, int sections,
         if (atomicAdd(bits + 63, 1u) == total - 1) {
             atomicExch(bits + 63, 0u);
             for (int q = 0; q < sections; ++q) {
-                const float m2 = __uint_as_float(atomicExch(bits + q, 0u));
-                float sc = 1.f;
-                if (m2 > 0.f && m2 < 3.0e38f) {
-                    int e;
-                    frexpf(m2, &e);
-                    int k = 10 - e;
-                    k = k > 60 ? 60 : (k < -60 ? -60 : k);
-                    sc = ldexpf(1.f, k);
-                }
-                scale2[4 * q] = sc;
-                scale2[4 * q + 1] = 1.f / sc;
+                store_scale2(scale2 + 4 * q, __uint_as_float(atomicExch(bits + q, 0u)));
             }
         }
     }
 }
 
-// scale2[s] = {2^k, 2^-k, -, -} with |x|max 2^k in [2^9, 2^10)  (same rule as csrc/conv3x3.hip); the maxima were
-// collected in bits[s], which is left ZERO for the next user (caller-owned scratch that travels zero between calls)
+// scale2[s] = {2^k, 2^-k, -, -} by the scale rule of csrc/f16x3_operand.h; the maxima were collected in bits[s], which is
+// left ZERO for the next user (caller-owned scratch that travels zero between calls)
 __global__ void scale_sections_kernel(float *__restrict__ scale2, unsigned *__restrict__ bits, int sections) {
     const int s = threadIdx.x;
     if (s >= sections) return;
     const float m = __uint_as_float(bits[s]);
     bits[s] = 0u;
-    float sc = 1.f;
-    if (m > 0.f && m < 3.0e38f) {
-        int e;
-        frexpf(m, &e);
-        int k = 10 - e;
-        k = k > 60 ? 60 : (k < -60 ? -60 : k);
-        sc = ldexpf(1.f, k);
-    }
-    scale2[4 * s] = sc;
-    scale2[4 * s + 1] = 1.f / sc;
+    store_scale2(scale2 + 4 * s, m);
 }
 
 }  // namespace attn

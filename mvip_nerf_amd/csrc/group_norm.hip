@@ -11,7 +11,7 @@
 //
 // Statistics are accumulated in fp64 (sum, sum of squares; var = E[x^2] - mean^2 evaluated in fp64),
 // partials are combined in a fixed order (no atomics): results are bit-reproducible run to run.
-#include "common.h"
+#include "f16x3_operand.h"
 
 namespace mvip {
 
@@ -132,7 +132,7 @@ __device__ __forceinline__ void group_totals(const double *__restrict__ part, in
 }
 
 // grid N*G, one wave: mean / rstd of each (sample, group) from the partials (used when the normalised
-// tensor is produced by another kernel, e.g. the split-plane writer of conv3x3.hip)
+// tensor is produced by another kernel, e.g. the split-plane writer of f16x3_producers.hip)
 __global__ void __launch_bounds__(64)
 gn_finalize_kernel(const double *__restrict__ part, int C, int64_t HW, int cpg, int chunks, float eps,
                    float *__restrict__ mean, float *__restrict__ rstd) {
@@ -271,44 +271,22 @@ gn_bwd_apply_kernel(const T *__restrict__ x, const T *__restrict__ dy, const T *
             const float xh = (v[k] - mu) * rs;
             d[k] = rs * (dh - m1 - xh * m2);
             if (ar) d[k] += e[k];
-            const float ab = fabsf(d[k]);
-            mx = (ab == ab && ab < 3.0e38f) ? fmaxf(mx, ab) : mx;           // the filter of cv_absmax_scale_kernel
+            mx = absmax_take(mx, d[k]);
         }
         store_vals<T, V>(or_ + i, d);
     }
     if (pmax) {                  // this workgroup's maximum of |dx|: one plain store, no atomics, no fence (see the header note)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-        __shared__ float wm[GN_THREADS / 64];
-        if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = mx;
-        __syncthreads();
-        if (threadIdx.x == 0) pmax[row * chunks + j] = fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]));
+        mx = block256_max(mx);
+        if (threadIdx.x == 0) pmax[row * chunks + j] = mx;
     }
 }
 
-// scale2 = {s, 1/s} from per-workgroup maxima (one workgroup; the power-of-two rule of cv_scale_kernel in conv3x3.hip)
+// scale2 = {s, 1/s} from per-workgroup maxima (one workgroup; the scale rule of f16x3_operand.h)
 __global__ void __launch_bounds__(256) gn_pmax_scale_kernel(const float *__restrict__ pmax, int64_t count, float *__restrict__ scale2) {
     float m = 0.f;
     for (int64_t i = threadIdx.x; i < count; i += 256) m = fmaxf(m, pmax[i]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    __shared__ float wm[4];
-    if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        m = fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]));
-        float sc = 1.f;
-        if (m > 0.f && m < 3.0e38f) {
-            int e;
-            frexpf(m, &e);
-            int k = 10 - e;
-            if (k > 60) k = 60;
-            if (k < -60) k = -60;
-            sc = ldexpf(1.f, k);
-        }
-        scale2[0] = sc;
-        scale2[1] = 1.f / sc;
-    }
+    m = block256_max(m);
+    if (threadIdx.x == 0) store_scale2(scale2, m);
 }
 
 template <typename T, int V>

@@ -25,6 +25,7 @@
 #include "mlp_layout.h"
 #include "mlp_device.h"
 #include "mlp_device_f16.h"
+#include "f16x3_operand.h"
 
 namespace mvip {
 using namespace mlp;
@@ -236,8 +237,7 @@ __device__ __forceinline__ f32x4 read_stage_piece(const float *tile, int row, in
 __global__ void absmax_kernel(const float *__restrict__ x, int64_t n, unsigned *__restrict__ out) {
     float m = 0.f;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float v = fabsf(x[i]);
-        m = (v == v && v < 3.0e38f) ? fmaxf(m, v) : m;
+        m = absmax_take(m, x[i]);
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));

@@ -9,23 +9,9 @@
 // registers 4 q .. 4 q + 3 of the two lanes (l32, 0) and (l32, 1).  One v_permlane32_swap per register pair trades the
 // halves, after which the lower half-wave owns the fragments q = 0, 2 and the upper one q = 1, 3 of its column.
 #pragma once
-#include "common.h"
+#include "f16x3_operand.h"
 
 namespace mvip {
-
-__device__ __forceinline__ void sink_split8(const float (&v)[8], uint4 &hi, uint4 &lo) {
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-    unsigned h[4], l[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        h2 a, b;
-        a.x = (_Float16)v[2 * i]; a.y = (_Float16)v[2 * i + 1];
-        b.x = (_Float16)(v[2 * i] - (float)a.x); b.y = (_Float16)(v[2 * i + 1] - (float)a.y);
-        h[i] = __builtin_bit_cast(unsigned, a); l[i] = __builtin_bit_cast(unsigned, b);
-    }
-    hi = make_uint4(h[0], h[1], h[2], h[3]);
-    lo = make_uint4(l[0], l[1], l[2], l[3]);
-}
 
 // v[16]: one accumulator tile's finished values of this lane.  Returns the two 8-row fragments this lane owns after
 // the exchange: frag[0] = rows 8 q0 .., frag[1] = rows 8 q1 .. with q0 = kg, q1 = 2 + kg.
@@ -66,13 +52,13 @@ __device__ __forceinline__ void sink_store_planes(char *planes_n, int64_t P, int
     uint4 hi, lo;
     const int b0 = blk8 + kg, b1 = blk8 + 2 + kg;
     if (col_ok && b0 < n_blk8) {
-        sink_split8(f0, hi, lo);
+        split8(f0, hi, lo);
         uint4 *dst = reinterpret_cast<uint4 *>(planes_n) + ((int64_t)(b0 >> 1) * 4 + (b0 & 1) * 2) * P + p;
         dst[0] = hi;
         if (write_lo) dst[P] = lo;                    // fp16 mode: the consumer fetches hi planes only
     }
     if (col_ok && b1 < n_blk8) {
-        sink_split8(f1, hi, lo);
+        split8(f1, hi, lo);
         uint4 *dst = reinterpret_cast<uint4 *>(planes_n) + ((int64_t)(b1 >> 1) * 4 + (b1 & 1) * 2) * P + p;
         dst[0] = hi;
         if (write_lo) dst[P] = lo;
@@ -89,7 +75,7 @@ __device__ __forceinline__ void sink_store_vfrag(char *vt, int s16, int lane, co
 #pragma unroll
         for (int j = 0; j < 8; ++j) t[j] = v[8 * s + j];
         uint4 hi, lo;
-        sink_split8(t, hi, lo);
+        split8(t, hi, lo);
         uint4 *dst = reinterpret_cast<uint4 *>(vt) + ((int64_t)(s16 + s) * 2) * 64 + lane;
         dst[0] = hi;
         if (write_lo) dst[64] = lo;

@@ -2,7 +2,7 @@
 // DS_NeRF/guidance/sd_utils.py:390-403; BasicTransformerBlock = LayerNorm -> self-attention -> LayerNorm ->
 // cross-attention -> LayerNorm -> GEGLU feed-forward, from the published SD-1.5 architecture), for activations
 // kept CHANNEL-MAJOR [N][C][LP] (LP = tokens padded to a multiple of 256) through the whole block: every linear
-// layer is then Y = W X on the split-precision GEMM of csrc/conv3x3.hip with no layout transposes, and these
+// layer is then Y = W X on the split-precision GEMM of csrc/gemm_f16x3.hip with no layout transposes, and these
 // kernels produce its operands:
 //   layernorm_split : per-token LayerNorm over the channel (strided) axis, written straight as fp16 hi/lo
 //                     split planes [N][C/16][2][2][LP][8] (the GEMM's B operand); two launches, both parallel over
@@ -12,25 +12,11 @@
 //   linear_small    : y = W act(x) + b for a handful of rows (the timestep embedding MLP and the per-ResNet-block
 //                     time projections, x of shape [2, 1280]) -- one wavefront per output feature, weights streamed
 //                     once, exact fp32.
-#include "common.h"
+#include "f16x3_operand.h"
 #include <stdlib.h>
 
 namespace mvip {
 namespace tok {
-
-__device__ __forceinline__ void split8(const float (&v)[8], uint4 &hi, uint4 &lo) {
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-    unsigned h[4], l[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        h2 a, b;
-        a.x = (_Float16)v[2 * i]; a.y = (_Float16)v[2 * i + 1];
-        b.x = (_Float16)(v[2 * i] - (float)a.x); b.y = (_Float16)(v[2 * i + 1] - (float)a.y);
-        h[i] = __builtin_bit_cast(unsigned, a); l[i] = __builtin_bit_cast(unsigned, b);
-    }
-    hi = make_uint4(h[0], h[1], h[2], h[3]);
-    lo = make_uint4(l[0], l[1], l[2], l[3]);
-}
 
 // LayerNorm statistics, pass 1: grid (LP / 64, C / 64, N), 256 threads: lane = token, wave = one 16-channel chunk of
 // the workgroup's 64-channel segment.  Per (sample, segment, token): sum and sum of squares in fp64 (exact enough
@@ -120,37 +106,15 @@ geglu_kernel(const float *__restrict__ y, int64_t R, int L, int LP, float *__res
         const float4 g = reinterpret_cast<const float4 *>(y + ((n * 2 * R + R + r) * LP))[p4];
         auto f = [&](float av, float gv, int k) {
             const float v = (p4 * 4 + k < L) ? av * (0.5f * gv * (1.0f + erff(gv * 0.70710678118654752f))) : 0.f;
-            const float w = fabsf(v);
-            m = (w == w && w < 3.0e38f) ? fmaxf(m, w) : m;
+            m = absmax_take(m, v);
             return v;
         };
         float4 o;
         o.x = f(a.x, g.x, 0); o.y = f(a.y, g.y, 1); o.z = f(a.z, g.z, 2); o.w = f(a.w, g.w, 3);
         reinterpret_cast<float4 *>(out + row * LP)[p4] = o;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    __shared__ float wm[4];
-    if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) atomicMax(bits, __float_as_uint(fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]))));
-}
-
-// scale2 = {2^k, 2^-k} from the maximum collected in *bits; *bits is left ZERO for its next user (the scratch word is
-// owned by the caller and travels zero between calls, which saves a zeroing launch per use)
-__global__ void scale_from_bits_kernel(float *__restrict__ scale2, unsigned *__restrict__ bits) {
-    const float m = __uint_as_float(*bits);
-    *bits = 0u;
-    float sc = 1.f;
-    if (m > 0.f && m < 3.0e38f) {
-        int e;
-        frexpf(m, &e);
-        int k = 10 - e;
-        k = k > 60 ? 60 : (k < -60 ? -60 : k);
-        sc = ldexpf(1.f, k);
-    }
-    scale2[0] = sc;
-    scale2[1] = 1.f / sc;
+    m = block256_max(m);
+    if (threadIdx.x == 0) atomicMax(bits, __float_as_uint(m));
 }
 
 // y[nb][m] = sum_k W[m][k] act(x[nb][k]) + b[m];  one wavefront per output feature m, NB <= 8 input rows.

@@ -17,7 +17,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 
-# Which layers take the hand-written split-precision kernels (csrc/conv3x3.hip) instead of the library ones;
+# Which layers take the hand-written split-precision kernels (csrc/conv3x3.hip, csrc/gemm_f16x3.hip) instead of the library ones;
 # switches exist for A/B timing (tools/sds_bench.py), every combination computes the same function.
 USE_MFMA_CONV3X3 = True
 USE_MFMA_CONV1X1 = True       # 1x1 shortcut convolutions on the split-precision GEMM: +0.2 ms per UNet forward against the
@@ -389,7 +389,7 @@ class VAEAttention(nn.Module):
     def forward(self, x):
         if x.is_cuda:
             from .. import ops
-            if USE_MFMA_VAE_ATTENTION and ops.vae_attention_supported(x):          # split-precision MFMA products (csrc/conv3x3.hip GEMM)
+            if USE_MFMA_VAE_ATTENTION and ops.vae_attention_supported(x):          # split-precision MFMA products (csrc/gemm_f16x3.hip)
                 return ops.vae_attention(x, self)
         B, C, H, W = x.shape
         h = self.group_norm(x).reshape(B, C, H * W).transpose(1, 2)
@@ -627,7 +627,7 @@ class SDNetworks:
         """fp16_weights (default): the random parameters are rounded to fp16-REPRESENTABLE values, kept in fp32 containers
         -- what the reference's networks hold in its default mode: it always loads the `revision="fp16"` checkpoint and
         casts it up to fp32 (DS_NeRF/guidance/sd_utils.py:69-74).  The split-precision kernels then run two products per
-        contraction step instead of three with bit-identical results (ops.TWO_PRODUCT, csrc/conv3x3.hip NP = 2).  False
+        contraction step instead of three with bit-identical results (ops.TWO_PRODUCT, csrc/conv3x3.hip and csrc/gemm_f16x3.hip NP = 2).  False
         keeps full fp32 random values (the three-product path: tests of both)."""
         g = torch.random.get_rng_state()
         torch.manual_seed(seed)

@@ -648,7 +648,7 @@ def conv3x3_supported(conv, x, hw=None):
     return ok
 
 
-# Arithmetic of the SDS networks' contractions (csrc/conv3x3.hip, attention.hip): 0 = split precision (fp16 hi + lo halves of
+# Arithmetic of the SDS networks' contractions (csrc/conv3x3.hip, gemm_f16x3.hip, attention.hip): 0 = split precision (fp16 hi + lo halves of
 # both operands, three products: fp32-grade, the fp32 networks), 1 = the reference's --fp16 mode (DS_NeRF/guidance/
 # sd_utils.py:66): one fp16 product, hi halves only.  Set for the duration of a network's forward by `precision(...)`
 # (guidance/sd_nets.py); autograd Functions remember it for their backward.
@@ -672,7 +672,7 @@ def _prec():
     return int(PREC)
 
 
-# Two products instead of three for weights that are exact fp16 values (prec = 2 of the C ABI; csrc/conv3x3.hip NP = 2).
+# Two products instead of three for weights that are exact fp16 values (prec = 2 of the C ABI; csrc/conv3x3.hip, gemm_f16x3.hip NP = 2).
 # The reference always loads `revision="fp16"` weights and, in its default fp32 mode, casts them UP
 # (DS_NeRF/guidance/sd_utils.py:69-74): the lo half of every frozen UNet / VAE weight is zero, the third product
 # W_lo . x_hi adds exact zeros, and skipping it (and the lo fragments' fetch) changes no bit of any result.  Decided per
@@ -1082,7 +1082,7 @@ def linear_cm(W, X, relu=False):
     return _LinearCM.apply(W, X, bool(relu))
 
 
-# Split-precision GEMM building blocks and the VAE mid-block attention built from them ------------------------
+# Split-precision GEMM building blocks (csrc/f16x3_producers.hip, csrc/gemm_f16x3.hip) and the VAE mid-block attention built from them ---
 
 ABSMAX_THREE_LAUNCHES = bool(int(_os.environ.get('MVIP_ABSMAX_THREE_LAUNCHES', '0')))     # A/B switch: zero + reduce + scale
 
@@ -1296,7 +1296,7 @@ def vae_attention(x, mod):
     return _VAEAttention.apply(x, mod)
 
 
-# 1x1 convolutions of the SDS networks on the split-precision GEMM ------------------------------------------------
+# 1x1 convolutions of the SDS networks on the split-precision GEMM (csrc/gemm_f16x3.hip) ---------------------------
 
 def conv1x1_supported(conv, x, tokens=False):
     """x: [N, Cin, H, W] (or [N, L, Cin] token-major when tokens=True), fp32 on the device."""

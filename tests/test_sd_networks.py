@@ -1,7 +1,7 @@
 """The SDS networks' COMPOSED HIP paths against the same sd_nets modules evaluated on the host in fp64 (their host branches
 are plain torch ops): the whole UNet forward and the whole VAE encoder, forward and data gradient, at the smallest sizes at
 which the hand-written kernels still run at every level.  Each kernel family (conv3x3.hip, group_norm.hip, attention.hip,
-transformer.hip, the split-precision GEMM) is pinned on its own elsewhere; here a stale power-of-two scale, a plane handed
+transformer.hip, the split-precision GEMM of gemm_f16x3.hip) is pinned on its own elsewhere; here a stale power-of-two scale, a plane handed
 to the wrong consumer, a hit of the _LAST_Y / _LAST_DX registries on the wrong tensor, the 22 grouped time projections
 handed to the wrong blocks, or an H / W transposition would show.
 

@@ -205,6 +205,115 @@ def test_absmax_scale_sections(cuda):
         assert 512.0 <= m * sc[s, 0] < 1024.0 and sc[s, 0] * sc[s, 1] == 1.0
 
 
+def _scale_rule(x):
+    """The scale rule of csrc/f16x3_operand.h restated in numpy: {s, 1/s} as fp32 for the tensor x."""
+    a = np.abs(np.asarray(x, dtype=np.float32).ravel())
+    a = a[~np.isnan(a) & (a < np.float32(3.0e38))]
+    m = np.float32(a.max()) if a.size else np.float32(0.0)
+    s = np.float32(1.0) if m == 0 else np.float32(2.0 ** int(np.clip(10 - np.frexp(np.float32(m))[1], -60, 60)))
+    return np.array([s, np.float32(1.0) / s], dtype=np.float32)
+
+
+def test_scale_rule_every_producer(cuda):
+    """Every producer of a power-of-two scale against the numpy restatement of the ONE rule, both words bit for bit."""
+    from mvip_nerf_amd import ops
+
+    def same(got, x, what):
+        got, want = np.ascontiguousarray(np.asarray(got.cpu() if torch.is_tensor(got) else got).ravel()[:2]), _scale_rule(x)
+        assert got.view(np.uint32).tolist() == want.view(np.uint32).tolist(), (what, got.tolist(), want.tolist())
+        return want
+
+    gen = torch.Generator().manual_seed(31)
+    # ops.absmax_scale, one launch and three: 49,157 floats = four workgroups, a trip of the 8-deep loop, the single-vector
+    # loop and the scalar tail; the same sliced [1:] (unaligned: the scalar path); 100 floats (one workgroup)
+    maxima = (0.0, 512.0, 1023.5, 0.3, 1e-30, 1e30)
+    expect = {0.0: 1.0, 512.0: 1.0, 1e-30: 2.0 ** 60, 1e30: 2.0 ** -60}
+    base = {49157: torch.rand(49157, generator=gen) * 1.8 - 0.9, 100: torch.rand(100, generator=gen) * 1.8 - 0.9}
+    old = ops.ABSMAX_THREE_LAUNCHES
+    try:
+        for three in (False, True):
+            ops.ABSMAX_THREE_LAUNCHES = three
+            for n, unit in base.items():
+                for i, mx in enumerate(maxima):
+                    for junk in (False, True):
+                        x = unit * mx                                    # |x| <= 0.9 mx, then the maximum itself
+                        x[(5, 4 * 9000 + 1, n - 1)[i % 3] % n] = -mx if i & 1 else mx    # 8-deep loop / vector loop / tail
+                        if junk:
+                            x[3], x[n // 2], x[n - 2] = float('nan'), float('inf'), 3.2e38
+                        xd = x.to(cuda)
+                        for off in ((0, 1) if n > 100 else (0,)):        # sliced on the device: a pointer 4 bytes off
+                            want = same(ops.absmax_scale(xd[off:]), x[off:], ('absmax_scale', three, n, mx, junk, off))
+                            if mx in expect:
+                                assert want[0] == np.float32(expect[mx])
+    finally:
+        ops.ABSMAX_THREE_LAUNCHES = old
+
+    # ops.absmax_scale_sections: an exact power of two in section 0, NaN / inf / 3.2e38 planted in sections 3, 2, 1
+    x = torch.randn(3, 4, 1001, generator=gen).clamp_(-4.0, 4.0)
+    x[:, 1] *= 100.0
+    x[:, 2] *= 1e-3
+    x[2, 0, 7] = -1024.0
+    x[1, 3, 5], x[0, 2, 1000], x[2, 1, 0] = float('nan'), float('inf'), 3.2e38
+    sc = N(ops.absmax_scale_sections(x.to(cuda), 3, 4, 1001)).reshape(4, 4)
+    for s in range(4):
+        want = same(sc[s], x[:, s], ('sections', s))
+    assert _scale_rule(x[:, 0])[0] == np.float32(0.5)
+
+    # ops.geglu: the rule on the tensor it returns.  value 64, gate 8: gelu(8) = 8 in fp32, the product is 512 exactly
+    Nb, R, L, LP = 2, 96, 200, 256
+    y = torch.randn(Nb, 2 * R, LP, generator=gen) * 2.0
+    for case in ('pow2', 'nan'):
+        yc = y.clone()
+        if case == 'pow2':
+            yc[1, 17, 33], yc[1, R + 17, 33] = 64.0, 8.0
+        else:
+            yc[0, 5, 9] = float('nan')
+        out, s2 = ops.geglu(yc.to(cuda), Nb, R, L, LP)
+        want = same(s2, N(out), ('geglu', case))
+        if case == 'pow2':
+            assert float(N(out)[1, 17, 33]) == 512.0 and want[0] == np.float32(1.0)
+        else:
+            assert np.isnan(N(out)[0, 5, 9])
+
+    # ops.gemm_geglu_f16x3 (the GEMM's epilogue collects the maximum): zero weight rows with bias 64 / 8 -> 512 exactly;
+    # a NaN bias -> one NaN row
+    K, P = 32, 256
+    xg = torch.randn(Nb, K, P, generator=gen)
+    s2x = ops.absmax_scale(xg.to(cuda))
+    xs = ops.split_planes_strided(xg.to(cuda), Nb, K, P, K * P, P, 1, s2x)
+    W = torch.randn(2 * R, K, generator=gen) / K ** 0.5
+    b = torch.randn(2 * R, generator=gen) * 0.2
+    for case in ('pow2', 'nan'):
+        Wc, bc = W.clone(), b.clone()
+        if case == 'pow2':
+            Wc[17], Wc[R + 17] = 0.0, 0.0
+            bc[17], bc[R + 17] = 64.0, 8.0
+        else:
+            bc[5] = float('nan')
+        wi, bi = ops.geglu_interleave(Wc.to(cuda), bc.to(cuda))
+        out, s2 = ops.gemm_geglu_f16x3(xs, ops.gemm_pack_a(wi, 2 * R, K, K, 1), bi, Nb, K, 2 * R, P, L, x_scale2=s2x)
+        want = same(s2, N(out), ('gemm_geglu', case))
+        if case == 'pow2':
+            assert float(N(out)[1, 17, 33]) == 512.0 and want[0] == np.float32(1.0)
+        else:
+            assert np.isnan(N(out)[0, 5, :L]).all()
+
+    # the {scale, 1/scale} words at the start of the packed images' 256-byte tails
+    for case in ('pow2', 'nan'):
+        w = torch.randn(32, 16, 3, 3, generator=gen).clamp_(-3.0, 3.0) * 0.05
+        a = torch.randn(32, 32, generator=gen).clamp_(-3.0, 3.0) * 0.05
+        if case == 'pow2':
+            w[7, 3, 1, 2], a[9, 30] = 0.25, -0.25
+        else:
+            w[7, 3, 1, 2], a[9, 30] = float('nan'), float('nan')
+        pk = ops.conv3x3_pack(w.to(cuda))
+        want = same(pk[32 * 16 * 36:32 * 16 * 36 + 8].view(torch.float32), w, ('conv3x3_pack', case))
+        pa = ops.gemm_pack_a(a.to(cuda), 32, 32, 32, 1)
+        want_a = same(pa[32 * 32 * 4:32 * 32 * 4 + 8].view(torch.float32), a, ('gemm_pack_a', case))
+        if case == 'pow2':
+            assert want[0] == np.float32(2048.0) and want_a[0] == np.float32(2048.0)
+
+
 # ---- contractions that hand each other operands (csrc/plane_sink.h) --------------------------------------------------
 def decode_planes(buf, Nb, rows, P):
     """fp16 hi/lo split planes [Nb][rows/16][kg 2][hl 2][P][8] -> float64 [Nb, rows, P] (hi + lo)."""
@@ -408,7 +517,7 @@ def test_unet_forward_has_no_library_attention_or_gemm(cuda):
 
 @pytest.mark.parametrize('cfg', [0, 1, 2, 3, 4, 5])
 def test_gemm_tile_configs_vs_fp64(cuda, cfg):
-    """Every workgroup-tile variant of the split-precision GEMM (csrc/conv3x3.hip) against W X in fp64, with bias,
+    """Every workgroup-tile variant of the split-precision GEMM (csrc/gemm_f16x3.hip) against W X in fp64, with bias,
     per-sample channel addend and residual, K from one to many 32-deep stages (pipeline prologue / tail)."""
     from mvip_nerf_amd import ops
     gen = torch.Generator().manual_seed(20 + cfg)

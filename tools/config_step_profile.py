@@ -42,7 +42,7 @@ with torch.profiler.profile(activities=[torch.profiler.ProfilerActivity.CUDA]) a
     torch.cuda.synchronize()
 ev = sorted([e for e in prof.key_averages() if e.device_time_total > 0], key=lambda e: -e.device_time_total)
 busy = sum(e.device_time_total for e in ev) / 1e3
-sds = sum(e.device_time_total for e in ev if any(t in e.key for t in ('conv3x3', 'gemm5', 'attn', 'cv_', 'gn_', 'tok::', 'gm_', 'softmax_rows', 'resize_bilinear', 'sds_'))) / 1e3
+sds = sum(e.device_time_total for e in ev if any(t in e.key for t in ('conv3x3', 'gemm5', 'attn', 'cv_', 'gn_', 'tok::', 'gm_', 'scale_from_bits', 'softmax_rows', 'resize_bilinear', 'sds_'))) / 1e3
 print(f'configs[{cfg}] iteration: wall {sorted(ts)[1]:.1f} ms {[round(t, 1) for t in ts]}, device-busy {busy:.1f} ms of which SD-network kernels {sds:.1f} ms, {sum(e.count for e in ev)} launches')
 rows = []
 for e in ev[:28]:

@@ -1,5 +1,5 @@
 """Register / LDS / scratch usage of the gfx950 kernels in one object of the in-tree build:
-    python tools/kernel_regs.py conv3x3 [name filter ...]
+    python tools/kernel_regs.py gemm_f16x3 [name filter ...]
 (extracts the .hip_fatbin of mvip_nerf_amd/lib/obj/<stem>.*.o, unbundles the gfx950 code object, reads the AMDGPU metadata
 notes).  A build-container tool: needs /opt/rocm/lib/llvm/bin."""
 import glob
