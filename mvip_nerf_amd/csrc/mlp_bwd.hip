@@ -22,7 +22,7 @@
 // ~90 FLOP/B -- still MFMA-bound at fp32 rates.
 #include "common.h"
 #include <stdlib.h>
-#include "mlp_layout.h"
+#include "mlp_image.h"
 #include "mlp_device.h"
 #include "mlp_device_f16.h"
 #include "f16x3_operand.h"
@@ -46,47 +46,11 @@ int mlp_delta16_prepare(const float *packed, float *image_t16, void *stream);
 int mlp_delta16_launch(const float *image_t16, const float *secb, const float *d_raw, int64_t p0, int64_t pc,
                        const float *act, int64_t act_n_pt, int64_t act_pt0, float *gst, int64_t n_pt, void *stream);
 
-// ------------------------------------------------------------------------------------------------
-// transposed weight image for B1
-// stream order: views^T (feature part), feature^T, then layers 7,6,5(h4 part),4,3,2,1 transposed
-// ------------------------------------------------------------------------------------------------
-constexpr int T_VIEWS_BLOCKS = 8 * 16;                 // out tiles: 256 feature units; K = 128 view units
-constexpr int T_LAYER_BLOCKS = 8 * 32;
-constexpr int T_TOTAL_BLOCKS = T_VIEWS_BLOCKS + 8 * T_LAYER_BLOCKS;      // 2176
-constexpr int T_TOTAL_CHUNKS = T_TOTAL_BLOCKS / CHUNK_BLOCKS;            // 136
-constexpr int T_FLOATS = T_TOTAL_BLOCKS * BLOCK_FLOATS;
+// transposed weight image for B1 (stream order and block counts: mlp_image.h), 32-point fragments from the 32-point image
 static_assert(T_VIEWS_BLOCKS % (NSLOT * CHUNK_BLOCKS) == 0, "ring phase");
 
-__device__ __forceinline__ float packed_w(const float *__restrict__ packed, int blk_off, int KG, int out, int k) {
-    const int blk = blk_off + block_pos(out >> 5, k >> 3, KG);
-    return packed[(int64_t)blk * BLOCK_FLOATS + ((k & 7) >> 2) * 128 + (out & 31) * 4 + (k & 3)];
-}
-
 __global__ void mlp_pack_transposed_kernel(const float *__restrict__ packed, float *__restrict__ pt) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= T_FLOATS) return;
-    const int blk = idx / BLOCK_FLOATS, r = idx % BLOCK_FLOATS;
-    const int h = r / 128, i = (r % 128) / 4, s = r % 4;
-    float v;
-    if (blk < T_VIEWS_BLOCKS) {
-        int ti, kg;
-        block_tile(blk, 16, ti, kg);
-        v = packed_w(packed, OFF_VIEWS, LV_KG, 8 * kg + 4 * h + s, 32 * ti + i);
-    } else {
-        const int m = (blk - T_VIEWS_BLOCKS) / T_LAYER_BLOCKS;      // 0: feature, 1..7: layers 7..1
-        const int local = (blk - T_VIEWS_BLOCKS) % T_LAYER_BLOCKS;
-        int ti, kg;
-        block_tile(local, 32, ti, kg);
-        const int out = 8 * kg + 4 * h + s, in = 32 * ti + i;
-        if (m == 0) v = packed_w(packed, OFF_FEAT, LH_KG, out, in);
-        else {
-            const int l = 8 - m;
-            if (l >= 6) v = packed_w(packed, OFF_L6 + (l - 6) * LH_BLOCKS, LH_KG, out, in);
-            else if (l == 5) v = packed_w(packed, OFF_L5, L5_KG, out, 64 + in);
-            else v = packed_w(packed, OFF_L1 + (l - 1) * LH_BLOCKS, LH_KG, out, in);
-        }
-    }
-    pt[idx] = v;
+    pack_transposed<Frag32, Frag32>(packed, pt);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -672,7 +636,7 @@ static int backward_impl(const float *packed, const float *a, const float *b, in
     static const bool delta16 = [] { const char *e = getenv("MVIP_DELTA16"); return e ? atoi(e) != 0 : true; }();
     if (precision == 1) { int rc = mlp_delta_f16x3_prepare(packed, packed_t, stream); if (rc != MVIP_OK) return rc; }
     else if (delta16) { int rc = mlp_delta16_prepare(packed, packed_t, stream); if (rc != MVIP_OK) return rc; }
-    else hipLaunchKernelGGL(mlp_pack_transposed_kernel, dim3((T_FLOATS + 255) / 256), dim3(256), 0, s, packed, packed_t);
+    else hipLaunchKernelGGL(mlp_pack_transposed_kernel, dim3(pack_transposed_grid<Frag32>()), dim3(PACK_THREADS), 0, s, packed, packed_t);
     const GemmTable tab = make_table(grads_host);
     hipLaunchKernelGGL(mlp_wgrad_table_kernel, dim3(1), dim3(64), 0, s, tab, tab_dev);
     unsigned *absmax = reinterpret_cast<unsigned *>(ws + T_FLOATS + TABLE_FLOATS - 4);   // tail of the table block

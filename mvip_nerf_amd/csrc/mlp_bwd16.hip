@@ -11,46 +11,15 @@
 // 32-point kernel's stash loads, stores and epilogues each cost matrix-pipe idle time (0.80 of peak); here they issue
 // under the SIMD partner's MFMAs.
 #include "mlp_device16.h"
+#include "mlp_image.h"
 
 namespace mvip {
 using namespace mlp;
 
-// the transposed stream: views^T (feature part), feature^T, then layers 7,6,5(h4 part),4,3,2,1 transposed
-constexpr int T16_VIEWS_BLOCKS = 16 * 8;               // 16 out tiles (256 feature units) x 8 in tiles (128 view units)
-constexpr int T16_LAYER_BLOCKS = 16 * 16;
-constexpr int T16_TOTAL_BLOCKS = T16_VIEWS_BLOCKS + 8 * T16_LAYER_BLOCKS;       // 2176, as the 32-point image
-constexpr int T16_TOTAL_CHUNKS = T16_TOTAL_BLOCKS / CHUNK_BLOCKS;
-constexpr int T16_FLOATS = T16_TOTAL_BLOCKS * BLOCK_FLOATS;
-
-__device__ __forceinline__ float packed_w32(const float *__restrict__ packed, int blk_off, int KG, int out, int k) {
-    const int blk = blk_off + block_pos(out >> 5, k >> 3, KG);
-    return packed[(int64_t)blk * BLOCK_FLOATS + ((k & 7) >> 2) * 128 + (out & 31) * 4 + (k & 3)];
-}
-
+// the transposed stream (mlp_image.h) in 16-point fragments, read from the 32-point image:
 // block (to, ti): lane (m, g) holds W^T[16 to + m][16 ti + 4 g + s] = W[16 ti + 4 g + s][16 to + m], s = 0..3
 __global__ void mlp_pack_transposed16_kernel(const float *__restrict__ packed, float *__restrict__ pt) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= T16_FLOATS) return;
-    const int blk = idx / BLOCK_FLOATS, r = idx % BLOCK_FLOATS;
-    const int lane = r / 4, s = r % 4, m = lane & 15, g = lane >> 4;
-    float v;
-    if (blk < T16_VIEWS_BLOCKS) {
-        const int to = blk / 8, ti = blk % 8;
-        v = packed_w32(packed, OFF_VIEWS, LV_KG, 16 * ti + 4 * g + s, 16 * to + m);
-    } else {
-        const int lm = (blk - T16_VIEWS_BLOCKS) / T16_LAYER_BLOCKS;        // 0: feature, 1..7: layers 7..1
-        const int local = (blk - T16_VIEWS_BLOCKS) % T16_LAYER_BLOCKS;
-        const int to = local / 16, ti = local % 16;
-        const int out = 16 * ti + 4 * g + s, in = 16 * to + m;
-        if (lm == 0) v = packed_w32(packed, OFF_FEAT, LH_KG, out, in);
-        else {
-            const int l = 8 - lm;
-            if (l >= 6) v = packed_w32(packed, OFF_L6 + (l - 6) * LH_BLOCKS, LH_KG, out, in);
-            else if (l == 5) v = packed_w32(packed, OFF_L5, L5_KG, out, 64 + in);
-            else v = packed_w32(packed, OFF_L1 + (l - 1) * LH_BLOCKS, LH_KG, out, in);
-        }
-    }
-    pt[idx] = v;
+    pack_transposed<Frag16, Frag32>(packed, pt);
 }
 
 namespace f16p {
@@ -66,7 +35,7 @@ mlp_delta16_kernel(const float *__restrict__ packed_t, const float *__restrict__
     const int64_t pl = (int64_t)blockIdx.x * WG_POINTS + wave * 16 + n;       // index inside [0, p_count)
     const bool live = pl < p_count;
 
-    Stream16 st{packed_t, lds, wave, lane, T16_TOTAL_CHUNKS};
+    Stream16 st{packed_t, lds, wave, lane, T_TOTAL_CHUNKS};
     for (int b = wave; b < SEC_B_FLOATS / BLOCK_FLOATS; b += 8)
         glds<0>(secb + b * BLOCK_FLOATS + lane * 4, lds + RING16_FLOATS + b * BLOCK_FLOATS);
     st.issue_chunk(0, 0);
@@ -121,7 +90,7 @@ mlp_delta16_kernel(const float *__restrict__ packed_t, const float *__restrict__
         [&](auto to, const f32x4 &acc, int) { gg[to.value] = acc; put(2 * GT_F + to.value, acc); });
 
     // G_7 = relu'(h7) . (W_feat^T g_feat + w_alpha d_sigma)
-    layer16x<T16_VIEWS_BLOCKS, 16, 16, false, false>(st, a, nullptr, [&](auto ti) { return gg[ti.value]; },
+    layer16x<T_VIEWS_BLOCKS, 16, 16, false, false>(st, a, nullptr, [&](auto ti) { return gg[ti.value]; },
         [&](auto to) { return act_tile(2 * (AT_H + 56) + to.value); },
         [&](auto to, const f32x4 &acc, const f32x4 &hv) {
             const f32x4 wa = *reinterpret_cast<const f32x4 *>(sb + SB_WALPHA + 16 * to.value + 4 * g);
@@ -137,7 +106,7 @@ mlp_delta16_kernel(const float *__restrict__ packed_t, const float *__restrict__
     // G_m = relu'(h_m) . W_{m+1}^T G_{m+1},  m = 6..0   (layer 5 contributes its h4 columns only)
     static_for<7>([&](auto mi) {
         constexpr int m = 6 - decltype(mi)::value;
-        layer16x<T16_VIEWS_BLOCKS + (7 - m) * T16_LAYER_BLOCKS, 16, 16, m == 0, false>(st, a, nullptr,
+        layer16x<T_VIEWS_BLOCKS + (7 - m) * T_LAYER_BLOCKS, 16, 16, m == 0, false>(st, a, nullptr,
             [&](auto ti) { return gg[ti.value]; },
             [&](auto to) { return act_tile(2 * (AT_H + 8 * m) + to.value); },
             [&](auto to, const f32x4 &acc, const f32x4 &hv) {
@@ -154,9 +123,9 @@ mlp_delta16_kernel(const float *__restrict__ packed_t, const float *__restrict__
 
 }  // namespace f16p
 
-// image_t16: T16_FLOATS floats (the same size as the 32-point transposed image, so it takes its place in the workspace)
+// image_t16: T_FLOATS floats (every transposed image has that size, so it takes the 32-point one's place in the workspace)
 int mlp_delta16_prepare(const float *packed, float *image_t16, void *stream) {
-    hipLaunchKernelGGL(mlp_pack_transposed16_kernel, dim3((T16_FLOATS + 255) / 256), dim3(256), 0, as_stream(stream), packed,
+    hipLaunchKernelGGL(mlp_pack_transposed16_kernel, dim3(pack_transposed_grid<Frag16>()), dim3(PACK_THREADS), 0, as_stream(stream), packed,
                        image_t16);
     return check_launch();
 }

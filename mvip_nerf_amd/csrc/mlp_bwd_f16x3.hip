@@ -3,54 +3,19 @@
 // arithmetic.  Gradients G_l are produced, masked, stored (fp32 stash) and re-split in registers
 // exactly like activations in the forward.
 #include "common.h"
-#include "mlp_layout.h"
+#include "mlp_image.h"
 #include "mlp_device.h"
 #include "mlp_device_f16.h"
 
 namespace mvip {
 using namespace mlp;
 
-constexpr int T16_VIEWS_BLOCKS = 8 * 8 * 2;            // 8 out tiles (feature units) x 8 k-steps x [hi|lo]
-constexpr int T16_LAYER_BLOCKS = 8 * 16 * 2;
-constexpr int T16_TOTAL_BLOCKS = T16_VIEWS_BLOCKS + 8 * T16_LAYER_BLOCKS;     // 2176, as the fp32 transposed image
-constexpr int T16_FLOATS = T16_TOTAL_BLOCKS * BLOCK_FLOATS;
-static_assert(T16_VIEWS_BLOCKS % F_GROUP_BLOCKS == 0 && T16_LAYER_BLOCKS % F_GROUP_BLOCKS == 0, "group alignment");
+static_assert(T_VIEWS_BLOCKS % F_GROUP_BLOCKS == 0 && T_LAYER_BLOCKS % F_GROUP_BLOCKS == 0, "group alignment");
 
-// W[out][k] of a layer (identified by its block offset / k-steps per tile) read back from the
-// forward f16x3 image: hi + lo is exact in fp32
-__device__ __forceinline__ float image16_w(const _Float16 *__restrict__ img, int blk_off, int ksn, int out, int k) {
-    const int ks = k >> 4, r = k & 15;
-    const int j = ((r >> 3) << 2) | (r & 3), h = (r & 7) >> 2;
-    const int64_t blk = blk_off + 2 * ((out >> 5) * ksn + ks);
-    const int64_t e = blk * 512 + ((h * 32 + (out & 31)) * 8 + j);
-    return (float)img[e] + (float)img[e + 512];
-}
-
+// the transposed stream (mlp_image.h) from the forward f16x3 image: each weight is read back as hi + lo (exact in fp32)
+// and split again
 __global__ void mlp_pack_transposed_f16x3_kernel(const _Float16 *__restrict__ img, _Float16 *__restrict__ out) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= T16_FLOATS * 2) return;
-    const int blk = idx / 512, e = idx % 512;
-    const int lane = e / 8, j = e % 8, h = lane / 32, i = lane % 32;
-    int local, ksn;
-    float w;
-    if (blk < T16_VIEWS_BLOCKS) { local = blk; ksn = 8; }
-    else { local = (blk - T16_VIEWS_BLOCKS) % T16_LAYER_BLOCKS; ksn = 16; }
-    const int pair = local / 2, lo = local % 2, ti = pair / ksn, ks = pair % ksn;
-    const int in = 32 * ti + i;                                   // row of W^T = input unit
-    const int o = 16 * ks + 8 * (j >> 2) + 4 * h + (j & 3);       // column of W^T = output unit
-    if (blk < T16_VIEWS_BLOCKS) w = image16_w(img, OFF_VIEWS, LV_KG / 2, o, in);
-    else {
-        const int m = (blk - T16_VIEWS_BLOCKS) / T16_LAYER_BLOCKS;        // 0: feature, 1..7: layers 7..1
-        if (m == 0) w = image16_w(img, OFF_FEAT, LH_KG / 2, o, in);
-        else {
-            const int l = 8 - m;
-            if (l >= 6) w = image16_w(img, OFF_L6 + (l - 6) * LH_BLOCKS, LH_KG / 2, o, in);
-            else if (l == 5) w = image16_w(img, OFF_L5, L5_KG / 2, o, 64 + in);
-            else w = image16_w(img, OFF_L1 + (l - 1) * LH_BLOCKS, LH_KG / 2, o, in);
-        }
-    }
-    const _Float16 wh = (_Float16)w;
-    out[idx] = lo ? (_Float16)(w - (float)wh) : wh;
+    pack_transposed<FragH32, FragH32>(img, out);
 }
 
 __global__ __launch_bounds__(256, 1) void mlp_delta_f16x3_kernel(
@@ -65,7 +30,7 @@ __global__ __launch_bounds__(256, 1) void mlp_delta_f16x3_kernel(
     const int64_t pl = pt * 32 + j;
     const bool live = pl < p_count;
 
-    StreamF st{img_t, lds, wave, lane, T16_TOTAL_BLOCKS};
+    StreamF st{img_t, lds, wave, lane, T_TOTAL_BLOCKS};
     st.init_bases();
     for (int b = wave; b < SEC_B_FLOATS / BLOCK_FLOATS; b += 4)
         glds16(secb + b * BLOCK_FLOATS + lane * 4, lds + F_RING_FLOATS + b * BLOCK_FLOATS);
@@ -140,7 +105,7 @@ __global__ __launch_bounds__(256, 1) void mlp_delta_f16x3_kernel(
         [&](auto ks) { return FragPair{gv[ks.value >> 1].hi[ks.value & 1], gv[ks.value >> 1].lo[ks.value & 1]}; },
         NoPre{}, [&](auto ti, const f32x16 &acc, int) { put(GT_F + ti.value, acc); g[ti.value] = split_tile(acc); });
     // G_7 = relu'(h7) . (W_feat^T g_feat + w_alpha d_sigma)
-    run_layer_f<T16_VIEWS_BLOCKS, 8, 16, false>(st, a0, a1,
+    run_layer_f<T_VIEWS_BLOCKS, 8, 16, false>(st, a0, a1,
         [&](auto ks) { return FragPair{g[ks.value >> 1].hi[ks.value & 1], g[ks.value >> 1].lo[ks.value & 1]}; },
         [&](auto ti) { return act_mask(56 + ti.value); },
         [&](auto ti, const f32x16 &acc, unsigned hv) {
@@ -159,7 +124,7 @@ __global__ __launch_bounds__(256, 1) void mlp_delta_f16x3_kernel(
     // G_m = relu'(h_m) . W_{m+1}^T G_{m+1},  m = 6..0
     static_for<7>([&](auto mi) {
         constexpr int idx = decltype(mi)::value, m = 6 - idx;
-        run_layer_f<T16_VIEWS_BLOCKS + (1 + idx) * T16_LAYER_BLOCKS, 8, 16, (idx == 6)>(st, a0, a1,
+        run_layer_f<T_VIEWS_BLOCKS + (1 + idx) * T_LAYER_BLOCKS, 8, 16, (idx == 6)>(st, a0, a1,
             [&](auto ks) { return FragPair{g[ks.value >> 1].hi[ks.value & 1], g[ks.value >> 1].lo[ks.value & 1]}; },
             [&](auto ti) { return act_mask(8 * m + ti.value); },
             [&](auto ti, const f32x16 &acc, unsigned hv) {
@@ -176,7 +141,7 @@ __global__ __launch_bounds__(256, 1) void mlp_delta_f16x3_kernel(
 
 // used by backward_impl (mlp_bwd.hip) when precision == 1
 int mlp_delta_f16x3_prepare(const float *image16, float *image_t16, void *stream) {
-    hipLaunchKernelGGL(mlp_pack_transposed_f16x3_kernel, dim3((T16_FLOATS * 2 + 255) / 256), dim3(256), 0,
+    hipLaunchKernelGGL(mlp_pack_transposed_f16x3_kernel, dim3(pack_transposed_grid<FragH32>()), dim3(PACK_THREADS), 0,
                        as_stream(stream), reinterpret_cast<const _Float16 *>(image16),
                        reinterpret_cast<_Float16 *>(image_t16));
     return check_launch();

@@ -1,37 +1,12 @@
 // Entry points of the two-waves-per-SIMD exact-fp32 forward (kernel: mlp_fwd16_kernel.h): the image pack, the unfolded
 // inference launches and the stash-writing training forward.  The folded inference launches are mlp_fwd16_fold.hip.
 #include "mlp_fwd16_kernel.h"
+#include "mlp_image.h"
 
 namespace mvip {
 namespace f16p {
 
-// ---- packing ---------------------------------------------------------------------------------------------------
-__global__ void mlp_pack16_kernel(ParamPtrsC16 pp, float *__restrict__ packed) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= SEC_A_FLOATS) return;
-    const int blk = idx / BLOCK_FLOATS, r = idx % BLOCK_FLOATS;
-    const int lane = r / 4, s = r % 4, m = lane & 15, g = lane >> 4;
-    int local, nti, param;
-    int layer = -1;                                   // 0..7 hidden, 8 feature, 9 views
-    if (blk < OFF_L1) { local = blk; nti = NTI_L0; layer = 0; }
-    else if (blk < OFF_L5) { layer = 1 + (blk - OFF_L1) / LH_BLOCKS; local = (blk - OFF_L1) % LH_BLOCKS; nti = NTI_LH; }
-    else if (blk < OFF_L6) { layer = 5; local = blk - OFF_L5; nti = NTI_L5; }
-    else if (blk < OFF_FEAT) { layer = 6 + (blk - OFF_L6) / LH_BLOCKS; local = (blk - OFF_L6) % LH_BLOCKS; nti = NTI_LH; }
-    else if (blk < OFF_VIEWS) { layer = 8; local = blk - OFF_FEAT; nti = NTI_LH; }
-    else { layer = 9; local = blk - OFF_VIEWS; nti = NTI_LV; }
-    const int to = local / nti, ti = local % nti;
-    const int row = 16 * to + m, col = 16 * ti + 4 * g + s;
-    float v = 0.f;
-    if (layer == 0) { if (col < 63) v = pp.p[P_W0][row * 63 + col]; }
-    else if (layer == 5) {
-        if (col < 63) v = pp.p[10][row * 319 + col];
-        else if (col >= 64) v = pp.p[10][row * 319 + 63 + (col - 64)];
-    }
-    else if (layer == 8) v = pp.p[P_WF][row * 256 + col];
-    else if (layer == 9) { if (col < 283) v = pp.p[P_WV][row * 283 + col]; }
-    else { param = 2 * layer; v = pp.p[param][row * 256 + col]; }
-    packed[idx] = v;
-}
+__global__ void mlp_pack16_kernel(ParamPtrs pp, float *__restrict__ packed) { pack_image<Frag16>(pp, packed); }
 
 }  // namespace f16p
 }  // namespace mvip
@@ -41,18 +16,11 @@ using namespace mvip::f16p;
 
 // packed16 = [section A in 16-point block order | section B copied from the 32-point image]
 extern "C" int mvip_mlp_pack16(const float *const *params_host, const float *packed32, float *packed16, void *stream) {
-    if (!params_host || !packed32 || !packed16) return MVIP_EINVAL;
-    ParamPtrsC16 pp;
-    for (int i = 0; i < mlp::P_COUNT; ++i) {
-        if (!params_host[i]) return MVIP_EINVAL;
-        pp.p[i] = params_host[i];
-    }
+    mlp::ParamPtrs pp;
+    if (!mlp::collect_params(params_host, pp) || !packed32 || !packed16) return MVIP_EINVAL;
     hipStream_t st = as_stream(stream);
-    hipLaunchKernelGGL(mlp_pack16_kernel, dim3((mlp::SEC_A_FLOATS + 255) / 256), dim3(256), 0, st, pp, packed16);
-    if (hipMemcpyAsync(packed16 + mlp::SEC_A_FLOATS, packed32 + mlp::SEC_A_FLOATS, mlp::SEC_B_FLOATS * sizeof(float),
-                       hipMemcpyDeviceToDevice, st) != hipSuccess)
-        return check_launch();
-    return check_launch();
+    hipLaunchKernelGGL(mlp_pack16_kernel, dim3(mlp::pack_image_grid<mlp::Frag16>()), dim3(mlp::PACK_THREADS), 0, st, pp, packed16);
+    return mlp::finish_with_section_b(packed16, packed32, st);
 }
 
 extern "C" int mvip_mlp_forward_rays16(const float *packed16, const float *rows, const float *z, int64_t B, int S,

@@ -24,6 +24,7 @@
 // MFMA (see mlp_device_f16.h); nothing the compiler knows about touches LDS inside the trunk.
 #include <stdlib.h>
 #include "mlp_device16.h"
+#include "mlp_image.h"
 
 namespace mvip {
 using namespace mlp;
@@ -41,8 +42,6 @@ constexpr int WG_POINTS = 128;
 constexpr int KS_L0 = 2, KS_LH = 8, KS_L5 = 10, KS_LV = 9;          // k-steps (32 input units) per output tile
 static_assert(16 * KS_L0 * 2 == L0_BLOCKS && 16 * KS_LH * 2 == LH_BLOCKS && 16 * KS_L5 * 2 == L5_BLOCKS &&
               8 * KS_LV * 2 == LV_BLOCKS, "same block counts as every other image");
-
-__host__ __device__ constexpr int unit_of(int g, int j) { return j < 4 ? 4 * g + j : 16 + 4 * g + (j - 4); }
 
 struct APairH { h16x8 h, l; };
 struct BPairH { h16x8 hi, lo; };
@@ -465,40 +464,7 @@ mlp_forward_f16x3_w16_kernel(const float *__restrict__ img, const float *__restr
 }
 
 // ---- packing ---------------------------------------------------------------------------------------------------
-struct ParamPtrsH { const float *p[P_COUNT]; };
-
-__device__ __forceinline__ float weight_at_h(const ParamPtrsH &pp, int layer_blk_off, int row, int k) {
-    // (layer identified by its block offset) -> W[row][k] with the fp32 image's K padding rules
-    if (layer_blk_off == OFF_L0) return k < 63 ? pp.p[P_W0][row * 63 + k] : 0.f;
-    if (layer_blk_off == OFF_L5) {
-        if (k < 63) return pp.p[10][row * 319 + k];
-        if (k >= 64) return pp.p[10][row * 319 + 63 + (k - 64)];
-        return 0.f;
-    }
-    if (layer_blk_off == OFF_VIEWS) return k < 283 ? pp.p[P_WV][row * 283 + k] : 0.f;
-    if (layer_blk_off == OFF_FEAT) return pp.p[P_WF][row * 256 + k];
-    if (layer_blk_off >= OFF_L6) return pp.p[2 * (6 + (layer_blk_off - OFF_L6) / LH_BLOCKS)][row * 256 + k];
-    return pp.p[2 * (1 + (layer_blk_off - OFF_L1) / LH_BLOCKS)][row * 256 + k];
-}
-
-__global__ void mlp_pack_f16x3_w16_kernel(ParamPtrsH pp, _Float16 *__restrict__ img) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;          // one fp16 element of section A
-    if (idx >= SEC_A_FLOATS * 2) return;
-    const int blk = idx / 512, e = idx % 512;                        // 512 halves per 1-KB block
-    const int lane = e / 8, j = e % 8, m = lane & 15, g = lane >> 4;
-    int off, ks;                                                      // layer block offset, k-steps per tile
-    if (blk < OFF_L1) { off = OFF_L0; ks = KS_L0; }
-    else if (blk < OFF_L5) { off = OFF_L1 + ((blk - OFF_L1) / LH_BLOCKS) * LH_BLOCKS; ks = KS_LH; }
-    else if (blk < OFF_L6) { off = OFF_L5; ks = KS_L5; }
-    else if (blk < OFF_FEAT) { off = OFF_L6 + ((blk - OFF_L6) / LH_BLOCKS) * LH_BLOCKS; ks = KS_LH; }
-    else if (blk < OFF_VIEWS) { off = OFF_FEAT; ks = KS_LH; }
-    else { off = OFF_VIEWS; ks = KS_LV; }
-    const int local = blk - off, pair = local / 2, lo = local % 2;   // [Ah | Al] per k-step
-    const int to = pair / ks, s = pair % ks;
-    const float w = weight_at_h(pp, off, 16 * to + m, 32 * s + unit_of(g, j));
-    const _Float16 wh = (_Float16)w;
-    img[idx] = lo ? (_Float16)(w - (float)wh) : wh;
-}
+__global__ void mlp_pack_f16x3_w16_kernel(ParamPtrs pp, _Float16 *__restrict__ img) { pack_image<FragH16>(pp, img); }
 
 template <bool FROM_RAYS>
 static int launch_w16(const float *img, const float *a, const float *b, int64_t P, int S, float *raw, float *stash, void *stream) {
@@ -531,19 +497,12 @@ using namespace mvip;
 // Image of the two-waves-per-SIMD split-precision forward: [section A as fp16 hi / lo fragments in 16x16x32 order | section B
 // copied from the fp32 image]; PACKED_FLOATS floats like every other image.
 extern "C" int mvip_mlp_pack_f16x3_w16(const float *const *params_host, const float *packed_f32, float *image, void *stream) {
-    if (!params_host || !image || !packed_f32) return MVIP_EINVAL;
-    f16h::ParamPtrsH pp;
-    for (int i = 0; i < mlp::P_COUNT; ++i) {
-        if (!params_host[i]) return MVIP_EINVAL;
-        pp.p[i] = params_host[i];
-    }
+    mlp::ParamPtrs pp;
+    if (!mlp::collect_params(params_host, pp) || !image || !packed_f32) return MVIP_EINVAL;
     hipStream_t s = as_stream(stream);
-    hipLaunchKernelGGL(f16h::mlp_pack_f16x3_w16_kernel, dim3((mlp::SEC_A_FLOATS * 2 + 255) / 256), dim3(256), 0, s, pp,
-                       reinterpret_cast<_Float16 *>(image));
-    if (hipMemcpyAsync(image + mlp::SEC_A_FLOATS, packed_f32 + mlp::SEC_A_FLOATS, sizeof(float) * mlp::SEC_B_FLOATS,
-                       hipMemcpyDeviceToDevice, s) != hipSuccess)
-        return check_launch();
-    return check_launch();
+    hipLaunchKernelGGL(f16h::mlp_pack_f16x3_w16_kernel, dim3(mlp::pack_image_grid<mlp::FragH16>()), dim3(mlp::PACK_THREADS), 0, s,
+                       pp, reinterpret_cast<_Float16 *>(image));
+    return mlp::finish_with_section_b(image, packed_f32, s);
 }
 
 // raw [B, S, 4] of the rays' sample points (rows [B, 11], depths z [B, S]): NeRF.forward under no_grad at

@@ -1,6 +1,7 @@
 // The folded inference network on the two-waves-per-SIMD exact-fp32 kernel (mlp_fwd16_kernel.h, FOLD = true): the pack of the
 // folded tail of the extended image and the folded twins of the four inference launches of mlp_fwd16.hip.
 #include "mlp_fwd16_kernel.h"
+#include "mlp_image.h"
 
 namespace mvip {
 namespace f16p {
@@ -14,7 +15,7 @@ namespace f16p {
 // the tile needs are staged in LDS first (one coalesced pass), so the 256-step sums read LDS instead of chasing global-memory
 // latency 256 times.  The ti == 0 workgroups also form b' of their 16 rows; the last workgroup copies section B.
 constexpr int FOLD_PACK_WV_LD = 257;                  // row pitch of the Wv tile in LDS (odd: the 16 rows hit 16 banks)
-__global__ void __launch_bounds__(256) mlp_fold_pack16_kernel(ParamPtrsC16 pp, float *__restrict__ packed) {
+__global__ void __launch_bounds__(256) mlp_fold_pack16_kernel(ParamPtrs pp, float *__restrict__ packed) {
     __shared__ float swv[16 * FOLD_PACK_WV_LD];
     __shared__ float swf[256 * 16];
     __shared__ float sbf[256];
@@ -24,14 +25,15 @@ __global__ void __launch_bounds__(256) mlp_fold_pack16_kernel(ParamPtrsC16 pp, f
             if (j < SB_BFOLD || j >= SB_BFOLD + 128) packed[FOLD_TAIL_B + j] = packed[SEC_A_FLOATS + j];
         return;
     }
+    constexpr LayerRow LV = LAYER[L_VIEWS];            // the folded blocks have the view layer's shape, order and padding
     const float *wv = pp.p[P_WV], *wf = pp.p[P_WF];
-    const int to = blk / NTI_LV, ti = blk % NTI_LV;
-    const int lane = t / 4, s = t % 4, m = lane & 15, g = lane >> 4;
-    const int row = 16 * to + m, c = 4 * g + s, col = 16 * ti + c;
+    int row, col, lo;
+    Frag16::decode(blk, t, LV.k_padded, row, col, lo);
+    const int to = row >> 4, m = row & 15, ti = col >> 4, c = col & 15;
     float v;
     if (ti < 16) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) swv[r * FOLD_PACK_WV_LD + t] = wv[(16 * to + r) * 283 + t];
+        for (int r = 0; r < 16; ++r) swv[r * FOLD_PACK_WV_LD + t] = wv[(16 * to + r) * LV.k_real + t];
 #pragma unroll
         for (int j = 0; j < 16; ++j) swf[(16 * j + t / 16) * 16 + t % 16] = wf[(16 * j + t / 16) * 256 + 16 * ti + t % 16];
         if (ti == 0) sbf[t] = pp.p[P_BF][t];
@@ -47,7 +49,7 @@ __global__ void __launch_bounds__(256) mlp_fold_pack16_kernel(ParamPtrsC16 pp, f
             packed[FOLD_TAIL_B + SB_BFOLD + 16 * to + t] = (float)(b + (double)pp.p[P_BV][16 * to + t]);
         }
     } else {
-        v = col < 283 ? wv[row * 283 + col] : 0.f;
+        v = weight_at(pp, LV, row, col);
     }
     packed[FOLD_TAIL_A + blk * BLOCK_FLOATS + t] = v;
 }
@@ -63,12 +65,8 @@ extern "C" int64_t mvip_mlp_packed_fold_floats(void) { return mlp::PACKED_FOLD_F
 // Fills the tail of an extended image (mvip_mlp_packed_fold_floats() floats) whose first mvip_mlp_packed_floats() floats
 // mvip_mlp_pack16 has already written on this stream: the folded view blocks and the section-B copy with the folded bias.
 extern "C" int mvip_mlp_fold_pack16(const float *const *params_host, float *packed16_ext, void *stream) {
-    if (!params_host || !packed16_ext) return MVIP_EINVAL;
-    ParamPtrsC16 pp;
-    for (int i = 0; i < mlp::P_COUNT; ++i) {
-        if (!params_host[i]) return MVIP_EINVAL;
-        pp.p[i] = params_host[i];
-    }
+    mlp::ParamPtrs pp;
+    if (!mlp::collect_params(params_host, pp) || !packed16_ext) return MVIP_EINVAL;
     hipLaunchKernelGGL(mlp_fold_pack16_kernel, dim3(mlp::FOLD_BLOCKS + 1), dim3(256), 0, as_stream(stream), pp, packed16_ext);
     return check_launch();
 }

@@ -265,9 +265,6 @@ mlp_forward16_kernel(const float *__restrict__ packed, const float *__restrict__
     }
 }
 
-// the 24 parameter tensors, as the pack kernels receive them
-struct ParamPtrsC16 { const float *p[P_COUNT]; };
-
 }  // namespace f16p
 }  // namespace mvip
 

@@ -16,7 +16,7 @@
 // Weight stream: [Ah | Al] 1-KB blocks per k-step, same byte size and layer offsets as the fp32
 // image, staged by LDS-DMA through a 2 x 64 KB ring (one barrier per 64 KB = 96 MFMAs per wave).
 #include "common.h"
-#include "mlp_layout.h"
+#include "mlp_image.h"
 #include "mlp_device.h"
 #include "mlp_device_f16.h"
 
@@ -24,41 +24,7 @@ namespace mvip {
 using namespace mlp;
 
 // ---------------------------------------------------------------------------------------------- pack
-struct ParamPtrsC { const float *p[P_COUNT]; };
-
-__device__ __forceinline__ float weight_at(const ParamPtrsC &pp, int layer_blk_off, int row, int k) {
-    // (layer identified by its block offset) -> W[row][k] with the fp32 image's K padding rules
-    if (layer_blk_off == OFF_L0) return k < 63 ? pp.p[P_W0][row * 63 + k] : 0.f;
-    if (layer_blk_off == OFF_L5) {
-        if (k < 63) return pp.p[10][row * 319 + k];
-        if (k >= 64) return pp.p[10][row * 319 + 63 + (k - 64)];
-        return 0.f;
-    }
-    if (layer_blk_off == OFF_VIEWS) return k < 283 ? pp.p[P_WV][row * 283 + k] : 0.f;
-    if (layer_blk_off == OFF_FEAT) return pp.p[P_WF][row * 256 + k];
-    if (layer_blk_off >= OFF_L6) return pp.p[2 * (6 + (layer_blk_off - OFF_L6) / LH_BLOCKS)][row * 256 + k];
-    return pp.p[2 * (1 + (layer_blk_off - OFF_L1) / LH_BLOCKS)][row * 256 + k];
-}
-
-__global__ void mlp_pack_f16x3_kernel(ParamPtrsC pp, _Float16 *__restrict__ img) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;          // one fp16 element of section A
-    if (idx >= SEC_A_FLOATS * 2) return;
-    const int blk = idx / 512, e = idx % 512;                        // 512 halves per 1-KB block
-    const int lane = e / 8, j = e % 8, h = lane / 32, i = lane % 32;
-    int off, ksn;                                                     // layer block offset, k-steps per tile
-    if (blk < OFF_L1) { off = OFF_L0; ksn = L0_KG / 2; }
-    else if (blk < OFF_L5) { off = OFF_L1 + ((blk - OFF_L1) / LH_BLOCKS) * LH_BLOCKS; ksn = LH_KG / 2; }
-    else if (blk < OFF_L6) { off = OFF_L5; ksn = L5_KG / 2; }
-    else if (blk < OFF_FEAT) { off = OFF_L6 + ((blk - OFF_L6) / LH_BLOCKS) * LH_BLOCKS; ksn = LH_KG / 2; }
-    else if (blk < OFF_VIEWS) { off = OFF_FEAT; ksn = LH_KG / 2; }
-    else { off = OFF_VIEWS; ksn = LV_KG / 2; }
-    const int local = blk - off, pair = local / 2, lo = local % 2;   // [Ah | Al] per k-step
-    const int ti = pair / ksn, ks = pair % ksn;
-    const int k = 16 * ks + 8 * (j >> 2) + 4 * h + (j & 3);
-    const float w = weight_at(pp, off, 32 * ti + i, k);
-    const _Float16 wh = (_Float16)w;
-    img[idx] = lo ? (_Float16)(w - (float)wh) : wh;
-}
+__global__ void mlp_pack_f16x3_kernel(ParamPtrs pp, _Float16 *__restrict__ img) { pack_image<FragH32>(pp, img); }
 
 template <bool FROM_RAYS, bool STASH>
 __global__ __launch_bounds__(256, 1) void mlp_forward_f16x3_kernel(
@@ -227,19 +193,12 @@ using namespace mvip;
 
 extern "C" int mvip_mlp_pack_f16x3(const float *const *params_host, float *image, const float *packed_f32,
                                    void *stream) {
-    if (!params_host || !image || !packed_f32) return MVIP_EINVAL;
-    ParamPtrsC pp;
-    for (int i = 0; i < mlp::P_COUNT; ++i) {
-        if (!params_host[i]) return MVIP_EINVAL;
-        pp.p[i] = params_host[i];
-    }
+    mlp::ParamPtrs pp;
+    if (!mlp::collect_params(params_host, pp) || !image || !packed_f32) return MVIP_EINVAL;
     hipStream_t s = as_stream(stream);
-    hipLaunchKernelGGL(mlp_pack_f16x3_kernel, dim3((mlp::SEC_A_FLOATS * 2 + 255) / 256), dim3(256), 0, s, pp,
+    hipLaunchKernelGGL(mlp_pack_f16x3_kernel, dim3(mlp::pack_image_grid<mlp::FragH32>()), dim3(mlp::PACK_THREADS), 0, s, pp,
                        reinterpret_cast<_Float16 *>(image));
-    // section B (fp32 biases / head rows) is shared with the fp32 image
-    hipMemcpyAsync(image + mlp::SEC_A_FLOATS, packed_f32 + mlp::SEC_A_FLOATS, sizeof(float) * mlp::SEC_B_FLOATS,
-                   hipMemcpyDeviceToDevice, s);
-    return check_launch();
+    return mlp::finish_with_section_b(image, packed_f32, s);
 }
 
 extern "C" int mvip_mlp_forward_rays_f16x3(const float *image, const float *rows, const float *z, int64_t B, int S,

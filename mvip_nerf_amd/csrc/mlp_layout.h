@@ -19,19 +19,15 @@
 // matrix pipe itself sustains 64.0 cycles per fp32 32x32x2 MFMA for dependent and independent chains alike.)
 //
 // Section B -- small vectors (biases, the 256->1 sigma row, the 128->3 rgb rows), natural order.
+//
+// This header is what the streaming kernels need: block counts and offsets.  What the blocks HOLD -- the layer table with
+// the K padding rule, the fragment map above (Frag32) and those of the three other images, the transposed stream -- is
+// defined once in mlp_image.h, which every pack kernel instantiates.
 #pragma once
 
 namespace mvip { namespace mlp {
 
 constexpr int BLOCK_FLOATS = 256;
-
-// position of block (tile ti, k-group kg) inside a layer with KG k-groups per tile, and its inverse
-__host__ __device__ constexpr int block_pos(int ti, int kg, int KG) { return (ti >> 1) * (2 * KG) + 2 * kg + (ti & 1); }
-__host__ __device__ inline void block_tile(int local, int KG, int &ti, int &kg) {
-    const int pair = local / (2 * KG), rem = local % (2 * KG);
-    kg = rem >> 1;
-    ti = 2 * pair + (rem & 1);
-}
 constexpr int CHUNK_BLOCKS = 16;                         // 16 KB staged per barrier
 constexpr int CHUNK_FLOATS = CHUNK_BLOCKS * BLOCK_FLOATS;
 
