@@ -977,6 +977,63 @@ int mvip_tsdf_fuse(const float *disp, const float *pose, const void *mask, int V
                    int nz, float x0, float y0, float z0, float x1, float y1, float z1, float trunc, float *tsdf, int *count,
                    void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mesh clean-up: vertex normals from the faces, Taubin smoothing, simplification by vertex clustering (beyond the
+ * reference, which has no mesh export; csrc/mesh_ops.hip, ops.mesh_corner_table / mesh_vertex_normals / mesh_smooth /
+ * mesh_cluster, mesh.vertex_normals / smooth / simplify).  The definitions, with their operation order, are written out
+ * in csrc/mesh_ops.hip and tests/mesh_ops_numpy.py.  All operands DEVICE memory, dense, except box / cells (host):
+ *   verts [V,3] fp32, faces [F,3] int32, colors [V,3] bytes or NULL; box = (origin[3], inv[3]) and cells[3] of the bit
+ *   grid above, inv = fp32(1 / cell) on all three axes; `cell` the same edge as a double.
+ * Every count is >= 0 and every V, 3 F, item and list count <= 2^31 - 1 (one more for the lists), a NULL operand that a
+ * non-zero count makes necessary, a bad box / cells / cell / placement / dedupe: MVIP_EINVAL (-1 from the size queries)
+ * before any device call.  Every launch goes on the caller's stream; no float atomics: all outputs are bit-reproducible.
+ * mvip_mesh_list_scratch_words: int32 words of `scratch` below (8-byte aligned).
+ * mvip_mesh_corner_table: for keys [n_items] in [0, n_lists): offsets [n_lists + 1], items [n_items];
+ *   items[offsets[k] : offsets[k+1]] = the i with keys[i] == k, ascending.  keys = the flattened faces, n_lists = V:
+ *   the corner table (corner c = 3 f + k is vertex faces[f,k]).  flag[0] = 1 iff a key lies outside [0, n_lists) (then
+ *   offsets / items are not to be used), else 0: the caller's one read.
+ * mvip_mesh_vertex_normals: normals [V,3] = normalised fp64 sum of (p1 - p0) x (p2 - p0) over the vertex's corners,
+ *   (0,0,0) for an empty list or a zero sum.  offsets / corners: the corner table of these faces, flag 0.
+ * mvip_mesh_smooth_pass: out = v + weight L(v), L(v) = (sum over v's corners of the two other vertices of the corner's
+ *   face) / (2 n_corners) - v in fp64; a vertex without corners is copied.  out is not verts; weight finite.
+ * mvip_mesh_rank_groups: workgroups of a rank pass over n items = int32 words of the `*_wg` workspaces (-1: bad n).
+ * mvip_mesh_cluster_assign: words [n_words(cells)] = the bits of the occupied cells; cell_of_vertex [V] (the linear cell,
+ *   -1 outside the box, which also sets flag[0]); word_rank [n_words], wg [rank_groups(n_words)]: workspace;
+ *   total[0] = the number of clusters; cluster_of_vertex [V] = rank of the vertex's cell among the set bits.
+ * mvip_mesh_gather: out[i] = map[idx[i]] (-1 where idx[i] is outside [0, n_map)): the faces remapped to clusters.
+ * mvip_mesh_cluster_place: rep [K,3] and rep_colors [K,3] (NULL iff colors is) per cluster from its member list
+ *   (mem_offsets / members: the table of keys = cluster_of_vertex) and corner list (cor_offsets / corners: the table of
+ *   keys = the remapped faces); placement 0 = mean, 1 = quadric with both fallbacks to the mean.
+ * mvip_mesh_cluster_faces: keep [F] (1: no two ids equal and, with dedupe, no earlier face with the same directed cycle),
+ *   referenced [K], their ranks face_rank [F] / cluster_rank [K] (workspaces face_wg, cluster_wg), totals[0] = faces kept,
+ *   totals[1] = clusters referenced: the caller's one read.
+ * mvip_mesh_cluster_emit: out_faces [n_out_faces,3] (kept faces in input order, renumbered), out_verts / out_colors
+ *   [n_out_verts,3] (referenced clusters in order), cluster_of_vertex [V] rewritten in place to the new numbering, -1 for
+ *   the vertices of dropped clusters. */
+int64_t mvip_mesh_list_scratch_words(int64_t n_items, int64_t n_lists);
+int mvip_mesh_corner_table(const int *keys, int64_t n_items, int64_t n_lists, int *offsets, int *items, int *scratch,
+                           int *flag, void *stream);
+int mvip_mesh_vertex_normals(const float *verts, const int *faces, int64_t n_verts, int64_t n_faces, const int *offsets,
+                             const int *corners, float *normals, void *stream);
+int mvip_mesh_smooth_pass(const float *verts, const int *faces, int64_t n_verts, int64_t n_faces, const int *offsets,
+                          const int *corners, double weight, float *out, void *stream);
+int64_t mvip_mesh_rank_groups(int64_t n);
+int mvip_mesh_cluster_assign(const float *verts, int64_t n_verts, const float *box, const int *cells, int *words,
+                             int *cell_of_vertex, int *word_rank, int *wg, int64_t *total, int *cluster_of_vertex, int *flag,
+                             void *stream);
+int mvip_mesh_gather(const int *idx, int64_t n, const int *map, int64_t n_map, int *out, void *stream);
+int mvip_mesh_cluster_place(const float *verts, const void *colors, const int *faces, int64_t n_verts, int64_t n_faces,
+                            const float *box, const int *cells, double cell, int64_t n_clusters, const int *mem_offsets,
+                            const int *members, const int *cor_offsets, const int *corners, const int *cell_of_vertex,
+                            int placement, float *rep, void *rep_colors, void *stream);
+int mvip_mesh_cluster_faces(const int *cluster_faces, int64_t n_faces, int64_t n_clusters, const int *cor_offsets,
+                            const int *corners, int dedupe, int *keep, int *referenced, int *face_wg, int *face_rank,
+                            int *cluster_wg, int *cluster_rank, int64_t *totals, void *stream);
+int mvip_mesh_cluster_emit(const int *cluster_faces, int64_t n_faces, const int *keep, const int *face_rank, const float *rep,
+                           const void *rep_colors, int64_t n_clusters, const int *referenced, const int *cluster_rank,
+                           int64_t n_verts, int64_t n_out_faces, int64_t n_out_verts, int *cluster_of_vertex, float *out_verts,
+                           void *out_colors, int *out_faces, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -204,6 +204,19 @@ _SIGNATURES = {
     'mvip_exemplar_finish': (_int, [_c_f, _i64, _int, _int, _int, _int, _int, _int, _c_f, _c_f, _c_f, _c_f, _c_f]),
     'mvip_tsdf_fuse': (_int, [_c_f, _c_f, _c_f, _int, _int, _int, _flt, _int, _int, _int, _flt, _flt, _flt, _flt, _flt, _flt, _flt,
                               _c_f, _c_f, _c_f]),
+    'mvip_mesh_list_scratch_words': (_i64, [_i64, _i64]),
+    'mvip_mesh_corner_table': (_int, [_c_f, _i64, _i64, _c_f, _c_f, _c_f, _c_f, _c_f]),
+    'mvip_mesh_vertex_normals': (_int, [_c_f, _c_f, _i64, _i64, _c_f, _c_f, _c_f, _c_f]),
+    'mvip_mesh_smooth_pass': (_int, [_c_f, _c_f, _i64, _i64, _c_f, _c_f, ctypes.c_double, _c_f, _c_f]),
+    'mvip_mesh_rank_groups': (_i64, [_i64]),
+    'mvip_mesh_cluster_assign': (_int, [_c_f, _i64, ctypes.POINTER(_flt), ctypes.POINTER(_int), _c_f, _c_f, _c_f, _c_f, _c_f, _c_f,
+                                        _c_f, _c_f]),
+    'mvip_mesh_gather': (_int, [_c_f, _i64, _c_f, _i64, _c_f, _c_f]),
+    'mvip_mesh_cluster_place': (_int, [_c_f, _c_f, _c_f, _i64, _i64, ctypes.POINTER(_flt), ctypes.POINTER(_int), ctypes.c_double,
+                                       _i64, _c_f, _c_f, _c_f, _c_f, _c_f, _int, _c_f, _c_f, _c_f]),
+    'mvip_mesh_cluster_faces': (_int, [_c_f, _i64, _i64, _c_f, _c_f, _int, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f]),
+    'mvip_mesh_cluster_emit': (_int, [_c_f, _i64, _c_f, _c_f, _c_f, _c_f, _i64, _c_f, _c_f, _i64, _i64, _i64, _c_f, _c_f, _c_f, _c_f,
+                                      _c_f]),
 }
 
 # every symbol include/mvip_nerf.h declares; tests check the built library exports all of them

@@ -5,6 +5,9 @@ the fused 8x256 MLP kernel for create_nerf, the fused hash-grid kernel for creat
 an indexed, crack-free triangle mesh with the HIP passes of csrc/mcubes.hip; extract_mesh() does both and colours the
 vertices; save_ply() writes the result.  fuse_depths() / extract_mesh_tsdf() mesh what the renderer sees instead: the
 rendered depth maps of the views fused into a truncated signed distance field (csrc/tsdf.hip), zero level set.  There is no CPU path: grids and meshes live on the device until save_ply.
+smooth() / simplify() / vertex_normals() clean the raw marching-cubes output up (csrc/mesh_ops.hip): Taubin smoothing
+against the lattice staircase, vertex clustering to a tenth of the triangles, and normals from the faces alone for a mesh
+that no longer sits on its lattice.
 
 Conventions (shared with csrc/mcubes.hip and the test restatement tests/mc_numpy.py): grid [nx, ny, nz], z fastest; point
 (i, j, k) sits at bmin + (i, j, k) * (bmax - bmin) / (n - 1), in fp32 arithmetic; a corner is inside iff sigma >= threshold
@@ -488,6 +491,33 @@ def extract_mesh_tsdf(render_kwargs, hwf, poses, near, far, bound_min, bound_max
     m = fuse_depths(disp, poses, float(hwf[2]), bound_min, bound_max, resolution, trunc, masks, largest, min_points)
     rgb = vertex_colors(render_kwargs, m.verts, m.normals, network) if colors else None
     return Mesh(m.verts, m.faces, m.normals, rgb)
+
+
+def vertex_normals(mesh):
+    """normals [V, 3] fp32 of `mesh` from its faces alone (ops.mesh_vertex_normals): area-weighted, outward for
+    counter-clockwise faces.  What a mesh that was cropped, smoothed or simplified needs in place of the lattice normals."""
+    return ops.mesh_vertex_normals(mesh.verts, mesh.faces)
+
+
+def smooth(mesh, iters=10, lam=0.5, mu=-0.53):
+    """Taubin smoothing (ops.mesh_smooth): a Mesh with the smoothed vertices, the faces and colours of `mesh` as they are
+    and the normals recomputed from the faces.  lam shrinks, mu < -lam inflates again: lattice-frequency noise goes, the
+    enclosed volume nearly stays (plain Laplacian smoothing, mu -> 0, shrinks the shape)."""
+    verts = ops.mesh_smooth(mesh.verts, mesh.faces, iters, lam, mu)
+    return Mesh(verts, mesh.faces, ops.mesh_vertex_normals(verts, mesh.faces), mesh.colors)
+
+
+def simplify(mesh, cell, placement='quadric', dedupe=False, origin=None):
+    """Simplification by vertex clustering (ops.mesh_cluster): every vertex in one cubic cell of edge `cell` (a bit grid that
+    starts at `origin`, default the componentwise minimum of the vertices; 1..512 cells per axis) becomes one vertex, placed
+    by `placement` ('quadric' or 'mean') inside that cell; faces that collapse are dropped; colours are the members' integer
+    means; normals are recomputed from the faces.  No vertex moves by more than sqrt(3) cell.
+
+    dedupe=False (the default) keeps a closed mesh closed: every directed edge stays balanced by its reverse, because a
+    collapsed face contributes (a, a), (a, b), (b, a), which cancel.  dedupe=True also drops repeated faces (same directed
+    cycle), which can break that balance."""
+    verts, faces, colors, _ = ops.mesh_cluster(mesh.verts, mesh.faces, mesh.colors, origin, cell, placement, dedupe)
+    return Mesh(verts, faces, ops.mesh_vertex_normals(verts, faces), colors)
 
 
 def frustum_bounds(poses, hwf, near, far):

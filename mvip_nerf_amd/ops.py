@@ -2463,3 +2463,243 @@ def exemplar_fill(images, masks, patch=7, rounds=3, iters=4, seed=0, sources=Non
     info = {'targets': s[:, 4].astype(np.int64), 'sources': s[:, 6].astype(np.int64), 'levels': s[:, 0].astype(np.int64),
             'energy': np.ascontiguousarray(s[:, 2:4]).view(np.int64).reshape(N).copy(), 'singular': s[:, 1] != 0, 'nnf': nnf}
     return out, info
+
+
+# mesh clean-up: corner table, vertex normals, Taubin smoothing, vertex clustering (beyond the reference, csrc/mesh_ops.hip) ------
+# The definitions are csrc/mesh_ops.hip's and tests/mesh_ops_numpy.py's.  There is no CPU path.
+
+MESH_PLACEMENTS = ('mean', 'quadric')
+MAX_CLUSTER_CELLS_PER_AXIS = 512
+
+
+def _mesh_operands(what, verts, faces, colors=None):
+    named = [('verts', verts, _F32), ('faces', faces, _I32)] + ([('colors', colors, torch.uint8)] if colors is not None else [])
+    for name, t, dtype in named:
+        if not torch.is_tensor(t):
+            raise ValueError(f'{what}: {name} must be a tensor on the GPU, got {type(t).__name__}')
+        if t.dtype != dtype:
+            raise ValueError(f'{what}: {name} must be {dtype}, got {t.dtype}')
+        if t.dim() != 2 or t.shape[1] != 3:
+            raise ValueError(f'{what}: {name} must be [{"F" if name == "faces" else "V"}, 3], got {tuple(t.shape)}')
+    tensors = [t.detach() for _, t, _ in named]
+    if not all(t.is_cuda for t in tensors):
+        raise ValueError(f'{what}: tensors on the GPU expected (the HIP path has no CPU path)')
+    if any(t.device != tensors[0].device for t in tensors):
+        raise ValueError(f'{what}: tensors on one device expected, got {sorted({str(t.device) for t in tensors})}')
+    if not all(t.is_contiguous() for t in tensors):
+        raise ValueError(f'{what}: every operand must be contiguous')
+    if colors is not None and colors.shape[0] != verts.shape[0]:
+        raise ValueError(f'{what}: colors {tuple(colors.shape)} for verts {tuple(verts.shape)}')
+    if verts.shape[0] > 2 ** 31 - 1 or 3 * faces.shape[0] > 2 ** 31 - 1:
+        raise ValueError(f'{what}: {verts.shape[0]} vertices / {faces.shape[0]} faces exceed int32 indices')
+    return tensors
+
+
+def _mesh_lists(keys, n_lists):
+    """(offsets [n_lists + 1], items [n], flag [1]) of mvip_mesh_corner_table for keys [n] int32; flag is NOT read here."""
+    n = int(keys.shape[0])
+    dev = keys.device
+    if n == 0 or n_lists == 0:
+        return (torch.zeros(n_lists + 1, device=dev, dtype=_I32), torch.empty(0, device=dev, dtype=_I32),
+                torch.full((1,), 1 if n else 0, device=dev, dtype=_I32))
+    words = _lib.load().mvip_mesh_list_scratch_words(n, n_lists)
+    if words < 0:
+        raise ValueError(f'mesh lists: {n} items in {n_lists} lists exceed int32 indices')
+    offsets = torch.empty(n_lists + 1, device=dev, dtype=_I32)
+    items = torch.empty(n, device=dev, dtype=_I32)
+    scratch = torch.empty(words, device=dev, dtype=_I32)
+    flag = torch.empty(1, device=dev, dtype=_I32)
+    call('mvip_mesh_corner_table', ptr(keys, _I32), n, n_lists, ptr(offsets, _I32), ptr(items, _I32), ptr(scratch, _I32),
+         ptr(flag, _I32), stream())
+    return offsets, items, flag
+
+
+def mesh_corner_table(faces, n_verts):
+    """The corner table of faces [F, 3] int32 on the device: (offsets [V + 1] int32, corners [3 F] int32).  Corner c = 3 f + k
+    is vertex faces[f, k]; the corners of vertex v are corners[offsets[v]:offsets[v + 1]] in ascending order.  F = 0 or V = 0:
+    empty tensors, nothing launched.  ValueError for a face index outside [0, V) (checked on the device, one flag read back:
+    the only synchronisation)."""
+    what = 'mesh_corner_table'
+    n_verts = int(n_verts)
+    if n_verts < 0 or n_verts > 2 ** 31 - 2:
+        raise ValueError(f'{what}: n_verts must be in 0..2^31 - 2, got {n_verts}')
+    if not torch.is_tensor(faces):
+        raise ValueError(f'{what}: faces must be a tensor on the GPU, got {type(faces).__name__}')
+    if faces.dtype != _I32:
+        raise ValueError(f'{what}: faces must be {_I32}, got {faces.dtype}')
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f'{what}: faces must be [F, 3], got {tuple(faces.shape)}')
+    if not faces.is_cuda:
+        raise ValueError(f'{what}: tensors on the GPU expected (the HIP path has no CPU path)')
+    if not faces.is_contiguous():
+        raise ValueError(f'{what}: every operand must be contiguous')
+    if 3 * faces.shape[0] > 2 ** 31 - 1:
+        raise ValueError(f'{what}: {faces.shape[0]} faces exceed int32 corner indices')
+    F = int(faces.shape[0])
+    if F and n_verts == 0:
+        raise ValueError(f'{what}: a face index lies outside [0, 0)')
+    offsets, corners, flag = _mesh_lists(faces.detach().reshape(-1), n_verts)
+    if F and int(flag.cpu()):
+        raise ValueError(f'{what}: a face index lies outside [0, {n_verts})')
+    return offsets, corners
+
+
+def mesh_vertex_normals(verts, faces):
+    """normals [V, 3] fp32 of an indexed mesh from its faces alone: per vertex the sum over its corner list of
+    (p1 - p0) x (p2 - p0) (area-weighted; faces counter-clockwise seen from outside, so it points outward), accumulated in
+    fp64, normalised, rounded to fp32; (0, 0, 0) for a vertex without faces or a zero sum."""
+    v, f = _mesh_operands('mesh_vertex_normals', verts, faces)
+    V, F = int(v.shape[0]), int(f.shape[0])
+    offsets, corners = mesh_corner_table(f, V)
+    normals = torch.empty((V, 3), device=v.device, dtype=_F32)
+    if V:
+        call('mvip_mesh_vertex_normals', ptr(v), ptr(f, _I32) if F else ptr(None), V, F, ptr(offsets, _I32),
+             ptr(corners, _I32) if F else ptr(None), ptr(normals), stream())
+    return normals
+
+
+def mesh_smooth(verts, faces, iters=10, lam=0.5, mu=-0.53):
+    """Taubin smoothing: new verts [V, 3] fp32.  One iteration is two gather passes, v <- v + lam L(v) then v <- v + mu L(v),
+    L(v) = (sum over v's corners of (a + b)) / (2 n_corners) - v with a, b the other two vertices of the corner's face (on a
+    closed manifold the uniform umbrella: every neighbour is in exactly two incident faces), summed in fp64 in corner order;
+    a pass reads only the previous pass's positions (two buffers in turn) and vertices without faces do not move.  The
+    corner table is built once.  ValueError for iters < 0, non-finite lam or mu, lam <= 0, mu >= 0, mu > -lam.  iters = 0: a
+    copy."""
+    import math
+    what = 'mesh_smooth'
+    v, f = _mesh_operands(what, verts, faces)
+    if int(iters) != iters or int(iters) < 0:
+        raise ValueError(f'{what}: iters must be an integer >= 0, got {iters!r}')
+    lam, mu = float(lam), float(mu)
+    if not (math.isfinite(lam) and math.isfinite(mu)) or lam <= 0 or mu >= 0 or mu > -lam:
+        raise ValueError(f'{what}: lam {lam} and mu {mu} must be finite with lam > 0 and mu <= -lam < 0')
+    V, F = int(v.shape[0]), int(f.shape[0])
+    cur = v.clone()
+    if int(iters) == 0 or V == 0:
+        return cur
+    offsets, corners = mesh_corner_table(f, V)
+    if F == 0:
+        return cur
+    nxt = torch.empty_like(cur)
+    for _ in range(int(iters)):
+        for w in (lam, mu):
+            call('mvip_mesh_smooth_pass', ptr(cur), ptr(f, _I32), V, F, ptr(offsets, _I32), ptr(corners, _I32), w, ptr(nxt), stream())
+            cur, nxt = nxt, cur
+    return cur
+
+
+def mesh_cluster_grid(lo, hi, cell, origin=None):
+    """The clustering lattice of mesh_cluster for vertices whose componentwise minimum / maximum are lo / hi (fp32 [3]):
+    (origin fp32 [3], inv fp32, cells (cx, cy, cz)).  origin defaults to lo; inv = fp32(1 / cell); the count of an axis is
+    floor(extent / cell) + 1 evaluated by the cell rule itself, floorf(fp32(hi - origin) * inv) + 1 in fp32, so the largest
+    vertex is in the last cell whatever the rounding.  ValueError for a cell that is not finite and > 0, non-finite
+    vertices or origin, a vertex below the origin, an axis of more than 512 cells (the message names the smallest
+    admissible cell)."""
+    import math
+    import numpy as np
+    what = 'mesh_cluster'
+    cell = float(cell)
+    if not (math.isfinite(cell) and cell > 0):
+        raise ValueError(f'{what}: cell must be finite and > 0, got {cell}')
+    lo, hi = np.asarray(lo, np.float32).reshape(3), np.asarray(hi, np.float32).reshape(3)
+    if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi))):
+        raise ValueError(f'{what}: a vertex is NaN or infinite')
+    o = lo if origin is None else np.asarray([float(x) for x in origin], np.float32)
+    if o.shape != (3,) or not np.all(np.isfinite(o)):
+        raise ValueError(f'{what}: origin must be three finite coordinates, got {origin!r}')
+    with np.errstate(over='ignore', divide='ignore'):
+        inv = np.float32(1.0 / cell)
+        n = np.floor((hi - o).astype(np.float32) * inv)
+    if not (math.isfinite(float(inv)) and inv > 0):
+        raise ValueError(f'{what}: 1 / cell is not a finite fp32 number > 0 for cell {cell}')
+    if np.any(lo < o) or np.any(n < 0):
+        raise ValueError(f'{what}: a vertex lies outside the box that starts at origin {o.tolist()}')
+    if np.any(n + 1 > MAX_CLUSTER_CELLS_PER_AXIS):
+        need = float(np.max(hi.astype(np.float64) - o.astype(np.float64))) / MAX_CLUSTER_CELLS_PER_AXIS
+        raise ValueError(f'{what}: cell {cell} gives {[int(x) + 1 for x in n]} cells, at most {MAX_CLUSTER_CELLS_PER_AXIS} per axis: '
+                         f'the smallest admissible cell is just above {need:.9g}')
+    return o, inv, tuple(int(x) + 1 for x in n)
+
+
+def mesh_cluster(verts, faces, colors, origin, cell, placement='quadric', dedupe=False):
+    """Simplification by vertex clustering (the definition: csrc/mesh_ops.hip, tests/mesh_ops_numpy.py): returns
+    (verts' [V', 3] fp32, faces' [F', 3] int32, colors' uint8 [V', 3] or None, cluster_of_vertex [V] int32: the new vertex of
+    each input vertex, -1 for the vertices of dropped clusters).
+
+    The clusters are the occupied cells of a bit grid (bitgrid.py) that starts at `origin` (None: the componentwise minimum of
+    the vertices) with cubic cells of edge `cell`, 1..512 per axis; ids ascend in (ix, iy, iz), z fastest.  placement 'mean':
+    the mean of the members; 'quadric': the minimiser of the summed squared distances to the area-weighted planes of the
+    cluster's corners, falling back to the mean when the system is near-singular or the minimiser leaves the cluster's own
+    cell -- so no vertex moves by more than sqrt(3) cell.  colors (uint8 [V, 3] or None): exact integer means.  Faces are
+    remapped, those with two equal ids dropped, the rest kept in input order; clusters that no surviving face references are
+    dropped and the rest renumbered in order.
+
+    dedupe=False is the default for a reason: a closed input (every directed edge (a, b) as often as (b, a)) stays closed,
+    because a collapsed face contributes (a, a), (a, b), (b, a), which cancel.  dedupe=True also drops every face whose
+    directed cycle, up to rotation, occurred earlier (the opposite orientation is a different face); removing duplicates can
+    break that balance.  ValueError for a vertex outside the box, NaN or infinite, a face index outside [0, V), more than 512
+    cells on an axis.  Reads back the vertex bounds, the cluster count and the two output sizes."""
+    import ctypes
+    import numpy as np
+    what = 'mesh_cluster'
+    v, f, *c = _mesh_operands(what, verts, faces, colors)
+    c = c[0] if c else None
+    if placement not in MESH_PLACEMENTS:
+        raise ValueError(f"{what}: placement must be 'mean' or 'quadric', got {placement!r}")
+    V, F = int(v.shape[0]), int(f.shape[0])
+    dev = v.device
+    if V == 0:
+        if F:
+            raise ValueError(f'{what}: a face index lies outside [0, 0)')
+        mesh_cluster_grid((0, 0, 0), (0, 0, 0), cell, origin)
+        return (torch.empty((0, 3), device=dev, dtype=_F32), torch.empty((0, 3), device=dev, dtype=_I32),
+                None if c is None else torch.empty((0, 3), device=dev, dtype=torch.uint8), torch.empty(0, device=dev, dtype=_I32))
+    lohi = torch.stack([v.amin(0), v.amax(0)]).cpu().numpy()
+    o, inv, cells = mesh_cluster_grid(lohi[0], lohi[1], cell, origin)
+    cbox = (ctypes.c_float * 6)(*([float(x) for x in o] + [float(inv)] * 3))
+    ccells = (ctypes.c_int * 3)(*cells)
+    lib = _lib.load()
+    st = stream()
+    nw = occupancy_words(cells)
+    words = torch.empty(nw, device=dev, dtype=_I32)
+    word_rank = torch.empty(nw, device=dev, dtype=_I32)
+    wg = torch.empty(max(1, lib.mvip_mesh_rank_groups(nw)), device=dev, dtype=_I32)
+    cellv = torch.empty(V, device=dev, dtype=_I32)
+    cov = torch.empty(V, device=dev, dtype=_I32)
+    meta = torch.empty(2, device=dev, dtype=torch.int64)                     # [0] the cluster count, [1] (low word) the flag
+    call('mvip_mesh_cluster_assign', ptr(v), V, cbox, ccells, ptr(words, _I32), ptr(cellv, _I32), ptr(word_rank, _I32),
+         ptr(wg, _I32), ptr(meta, torch.int64), ptr(cov, _I32), ctypes.c_void_p(meta.data_ptr() + 8), st)
+    K, outside = (int(x) for x in meta.cpu().numpy().view(np.int32)[[0, 2]])
+    if outside:
+        raise ValueError(f'{what}: a vertex lies outside the box that starts at origin {o.tolist()}, or is NaN or infinite')
+    rf = torch.empty(3 * F, device=dev, dtype=_I32)
+    if F:
+        call('mvip_mesh_gather', ptr(f, _I32), 3 * F, ptr(cov, _I32), V, ptr(rf, _I32), st)
+    mem_off, mem, _ = _mesh_lists(cov, K)
+    cor_off, cor, bad = _mesh_lists(rf, K)
+    if F and int(bad.cpu()):
+        raise ValueError(f'{what}: a face index lies outside [0, {V})')
+    rep = torch.empty((K, 3), device=dev, dtype=_F32)
+    repc = None if c is None else torch.empty((K, 3), device=dev, dtype=torch.uint8)
+    none = ptr(None)
+    call('mvip_mesh_cluster_place', ptr(v), ptr(c, torch.uint8), ptr(f, _I32) if F else none, V, F, cbox, ccells, float(cell), K,
+         ptr(mem_off, _I32), ptr(mem, _I32), ptr(cor_off, _I32), ptr(cor, _I32) if F else none, ptr(cellv, _I32),
+         MESH_PLACEMENTS.index(placement), ptr(rep), ptr(repc, torch.uint8), st)
+    keep = torch.empty(F, device=dev, dtype=_I32)
+    frank = torch.empty(F, device=dev, dtype=_I32)
+    fwg = torch.empty(max(1, lib.mvip_mesh_rank_groups(F)), device=dev, dtype=_I32)
+    ref = torch.empty(K, device=dev, dtype=_I32)
+    crank = torch.empty(K, device=dev, dtype=_I32)
+    cwg = torch.empty(max(1, lib.mvip_mesh_rank_groups(K)), device=dev, dtype=_I32)
+    totals = torch.empty(2, device=dev, dtype=torch.int64)
+    pf = (lambda t: ptr(t, _I32) if F else none)
+    call('mvip_mesh_cluster_faces', pf(rf), F, K, ptr(cor_off, _I32), pf(cor), int(bool(dedupe)), pf(keep), ptr(ref, _I32),
+         ptr(fwg, _I32), pf(frank), ptr(cwg, _I32), ptr(crank, _I32), ptr(totals, torch.int64), st)
+    F2, V2 = (int(x) for x in totals.cpu())
+    out_v = torch.empty((V2, 3), device=dev, dtype=_F32)
+    out_c = None if c is None else torch.empty((V2, 3), device=dev, dtype=torch.uint8)
+    out_f = torch.empty((F2, 3), device=dev, dtype=_I32)
+    call('mvip_mesh_cluster_emit', pf(rf), F, pf(keep), pf(frank), ptr(rep), ptr(repc, torch.uint8), K, ptr(ref, _I32),
+         ptr(crank, _I32), V, F2, V2, ptr(cov, _I32), ptr(out_v) if V2 else none, ptr(out_c, torch.uint8) if V2 else none,
+         ptr(out_f, _I32) if F2 else none, st)
+    return out_v, out_f, out_c, cov

@@ -4,13 +4,19 @@ binary PLY (mvip_nerf_amd/mesh.py).  Prints sigma percentiles of the grid (to ch
 
   python tools/extract_mesh.py CKPT.tar --out mesh.ply [--model mlp|tcnn] [--bound-min x y z --bound-max x y z]
          [--resolution 256] [--threshold 10] [--network fine|coarse] [--precision fp32|split] [--no-colors]
-         [--keep-largest K] [--min-component N]
+         [--keep-largest K] [--min-component N] [--smooth ITERS] [--simplify STEPS] [--simplify-placement quadric|mean]
   python tools/extract_mesh.py --tsdf --fixture [--iters 1500] --out mesh.ply [--trunc T] [--view-step S] ...
   python tools/extract_mesh.py --tsdf CKPT.tar --datadir SCENE [--factor 4] --out mesh.ply [--trunc T] [--view-step S] ...
 
 --keep-largest K keeps the K largest connected components of the inside lattice points, --min-component N those of at
 least N points (mesh.remove_floaters, connectivity 6; both: a component must meet both); the counts before and after are
 printed.
+
+--smooth ITERS runs ITERS Taubin iterations on the extracted mesh (mesh.smooth; 0, the default: off), --simplify STEPS then
+clusters its vertices in cubic cells of STEPS times the largest lattice step (mesh.simplify, --simplify-placement quadric or
+mean; 0, the default: off).  Both come after the floater options and recompute the normals from the faces; the colours are
+those of the extracted vertices (averaged per cluster).  The triangle and vertex counts before and after are printed.
+Without the two flags the file is what it was.
 
 --tsdf meshes what the renderer sees instead of thresholding sigma (mesh.fuse_depths): the disparity of every view (every
 S-th with --view-step S) is rendered and fused into a truncated signed distance field whose zero level set is extracted
@@ -64,6 +70,25 @@ def _timed(fn):
     return out, time.perf_counter() - t0
 
 
+def clean_up(a, m, lo, hi, res):
+    """--smooth, then --simplify, on the Mesh m extracted on the lattice `res` of the box [lo, hi]; (mesh, seconds)."""
+    if not a.smooth and not a.simplify:
+        return m, 0.0
+    res3 = (res,) * 3 if np.isscalar(res) else tuple(res)
+    lo32, hi32 = mesh._bounds(lo, hi)
+    h = max(float((hi32[k] - lo32[k]) / np.float32(res3[k] - 1)) for k in range(3))
+
+    def run():
+        out = mesh.smooth(m, a.smooth) if a.smooth else m
+        return mesh.simplify(out, a.simplify * h, a.simplify_placement) if a.simplify else out
+    out, t = _timed(run)
+    what = ' + '.join(([f'{a.smooth} Taubin iterations'] if a.smooth else [])
+                      + ([f'clustering at {a.simplify:g} lattice steps ({a.simplify_placement})'] if a.simplify else []))
+    print(f'{what}: {m.faces.shape[0]} triangles, {m.verts.shape[0]} vertices -> {out.faces.shape[0]} triangles, '
+          f'{out.verts.shape[0]} vertices')
+    return out, t
+
+
 def main_tsdf(ap, a, res, dev):
     """--tsdf: render the views' disparities, fuse them, extract the zero level set over the observed cells."""
     from mvip_nerf_amd import prepare
@@ -99,10 +124,11 @@ def main_tsdf(ap, a, res, dev):
         print(f'components of the inside points: {n_before} -> {n_after} kept')
     (verts, faces, normals), t_mc = _timed(lambda: mesh.marching_cubes(g, 1.0, lo32, hi32, valid=valid))
     colors, t_col = (None, 0.0) if a.no_colors else _timed(lambda: mesh.vertex_colors(te, verts, normals, a.network))
-    _, t_ply = _timed(lambda: mesh.save_ply(a.out, mesh.Mesh(verts, faces, normals, colors)))
-    print(f'tsdf zero level set: {verts.shape[0]} vertices, {faces.shape[0]} triangles -> {a.out}')
+    m, t_clean = clean_up(a, mesh.Mesh(verts, faces, normals, colors), lo32, hi32, res)
+    _, t_ply = _timed(lambda: mesh.save_ply(a.out, m))
+    print(f'tsdf zero level set: {m.verts.shape[0]} vertices, {m.faces.shape[0]} triangles -> {a.out}')
     print(f'time  model {t_model * 1e3:.1f} ms  render {t_render * 1e3:.1f} ms  fusion {t_fuse * 1e3:.1f} ms  components {t_cc * 1e3:.1f} ms  '
-          f'marching cubes {t_mc * 1e3:.1f} ms  colours {t_col * 1e3:.1f} ms  write {t_ply * 1e3:.1f} ms')
+          f'marching cubes {t_mc * 1e3:.1f} ms  colours {t_col * 1e3:.1f} ms  clean-up {t_clean * 1e3:.1f} ms  write {t_ply * 1e3:.1f} ms')
     return 0
 
 
@@ -120,6 +146,10 @@ def main(argv=None):
     ap.add_argument('--no-colors', action='store_true')
     ap.add_argument('--keep-largest', type=int, default=None, metavar='K', help='keep the K largest components')
     ap.add_argument('--min-component', type=int, default=None, metavar='N', help='drop components below N lattice points')
+    ap.add_argument('--smooth', type=int, default=0, metavar='ITERS', help='Taubin smoothing iterations (0: off)')
+    ap.add_argument('--simplify', type=float, default=0.0, metavar='STEPS',
+                    help='cluster the vertices in cells of STEPS times the largest lattice step (0: off)')
+    ap.add_argument('--simplify-placement', choices=('quadric', 'mean'), default='quadric')
     ap.add_argument('--tsdf', action='store_true', help='fuse rendered depth maps instead of thresholding sigma')
     ap.add_argument('--fixture', action='store_true', help='--tsdf: train the scene-1 fixture and use its cameras')
     ap.add_argument('--iters', type=int, default=1500, help='training iterations of --fixture')
@@ -128,6 +158,8 @@ def main(argv=None):
     ap.add_argument('--trunc', type=float, default=None, help='--tsdf: truncation distance (default: 4 lattice steps)')
     ap.add_argument('--view-step', type=int, default=1, metavar='S', help='--tsdf: fuse every S-th view')
     a = ap.parse_args(argv)
+    if a.smooth < 0 or not a.simplify >= 0:
+        ap.error('--smooth and --simplify must be >= 0')
     res = a.resolution[0] if len(a.resolution) == 1 else tuple(a.resolution)
     dev = torch.device('cuda', 0)
     if a.tsdf:
@@ -161,10 +193,11 @@ def main(argv=None):
         print(f'components of the inside points: {n_before} -> {n_after} kept')
     (verts, faces, normals), t_mc = timed(lambda: mesh.marching_cubes(grid, a.threshold, a.bound_min, a.bound_max))
     colors, t_col = (None, 0.0) if a.no_colors else timed(lambda: mesh.vertex_colors(kw, verts, normals, a.network))
-    _, t_ply = timed(lambda: mesh.save_ply(a.out, mesh.Mesh(verts, faces, normals, colors)))
-    print(f'threshold {a.threshold}: {verts.shape[0]} vertices, {faces.shape[0]} triangles -> {a.out}')
+    m, t_clean = clean_up(a, mesh.Mesh(verts, faces, normals, colors), a.bound_min, a.bound_max, res)
+    _, t_ply = timed(lambda: mesh.save_ply(a.out, m))
+    print(f'threshold {a.threshold}: {m.verts.shape[0]} vertices, {m.faces.shape[0]} triangles -> {a.out}')
     print(f'time  density grid {t_grid * 1e3:.1f} ms  components {t_cc * 1e3:.1f} ms  marching cubes {t_mc * 1e3:.1f} ms  colours {t_col * 1e3:.1f} ms  '
-          f'write {t_ply * 1e3:.1f} ms')
+          f'clean-up {t_clean * 1e3:.1f} ms  write {t_ply * 1e3:.1f} ms')
     return 0
 
 
