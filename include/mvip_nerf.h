@@ -1034,6 +1034,31 @@ int mvip_mesh_cluster_emit(const int *cluster_faces, int64_t n_faces, const int 
                            int64_t n_verts, int64_t n_out_faces, int64_t n_out_verts, int *cluster_of_vertex, float *out_verts,
                            void *out_colors, int *out_faces, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mesh rasterisation: per view the disparity, face-id and colour maps a mesh presents (beyond the reference, which has no
+ * mesh export and no rasteriser: neither entry point has a reference call site; csrc/raster.hip, ops.mesh_rasterize,
+ * mesh.render_views / visible_faces).  The definition, in fp64 and integers with its operation order, is written out in
+ * csrc/raster.hip and tests/raster_numpy.py: the conventions of mvip_tsdf_fuse (poses [V,3,4] camera-to-world, looking
+ * down -z, no half-pixel offset, disparity = 1 / planar depth), 8 sub-pixel bits, the top-left fill rule, no near-plane
+ * clipping (a face with a vertex nearer than znear or outside the guard band of 16,384 pixels is dropped whole).  All
+ * operands DEVICE memory, dense: verts [Nv,3] fp32, faces [F,3] int32, poses [V,3,4] fp32, colors [Nv,3] bytes or NULL,
+ * keys [V,H,W] 64-bit words.  MVIP_EINVAL before any device call for: a negative count, Nv, 3 F or V > 2^31 - 1, H or W
+ * outside 1..16384, focal or znear not finite and > 0, cull not 0 (none) or 1 (back-facing dropped), a NULL operand that a
+ * non-zero count makes necessary, rgb given without colors (Nv > 0).  V = 0, F = 0 and Nv = 0 are valid.  Every
+ * launch goes on the caller's stream; integer atomics only: the outputs are bit-reproducible.
+ * mvip_raster_fragments: clears keys, flag[0] and stats, then leaves in keys[v,y,x] the largest
+ *   (bits(D) << 32) | (0xFFFFFFFF - face) over the fragments of the pixel, 0 where there is none.  flag[0] = 1 iff a face
+ *   index lies outside [0, Nv) (such a face is dropped): the caller's one read.  stats: NULL, or two 64-bit words that
+ *   receive the fragments that passed every test and the atomics actually sent (a measuring variant of the kernel).
+ * mvip_raster_resolve: disp [V,H,W] fp32 (0 where empty), face [V,H,W] int32 (-1 where empty) and, iff rgb is not NULL,
+ *   rgb [V,H,W,3] bytes (0 where empty) from the keys of mvip_raster_fragments for the same mesh, poses and camera. */
+int mvip_raster_fragments(const float *verts, const int *faces, int64_t n_verts, int64_t n_faces, const float *poses,
+                          int64_t n_views, int H, int W, double focal, double znear, int cull, void *keys, int *flag,
+                          void *stats, void *stream);
+int mvip_raster_resolve(const void *keys, const float *verts, const int *faces, const void *colors, int64_t n_verts,
+                        int64_t n_faces, const float *poses, int64_t n_views, int H, int W, double focal, double znear,
+                        float *disp, int *face, void *rgb, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -217,6 +217,10 @@ _SIGNATURES = {
     'mvip_mesh_cluster_faces': (_int, [_c_f, _i64, _i64, _c_f, _c_f, _int, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f]),
     'mvip_mesh_cluster_emit': (_int, [_c_f, _i64, _c_f, _c_f, _c_f, _c_f, _i64, _c_f, _c_f, _i64, _i64, _i64, _c_f, _c_f, _c_f, _c_f,
                                       _c_f]),
+    'mvip_raster_fragments': (_int, [_c_f, _c_f, _i64, _i64, _c_f, _i64, _int, _int, ctypes.c_double, ctypes.c_double, _int, _c_f,
+                                     _c_f, _c_f, _c_f]),
+    'mvip_raster_resolve': (_int, [_c_f, _c_f, _c_f, _c_f, _i64, _i64, _c_f, _i64, _int, _int, ctypes.c_double, ctypes.c_double,
+                                   _c_f, _c_f, _c_f, _c_f]),
 }
 
 # every symbol include/mvip_nerf.h declares; tests check the built library exports all of them

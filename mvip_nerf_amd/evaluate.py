@@ -162,6 +162,50 @@ def evaluate_views(render_kwargs, hwf, poses, images, near, far, masks=None, dis
     return summarise(per_view)
 
 
+def mesh_depth_metrics(mesh, hwf, poses, disparities, masks=None, near=1e-3, cull='none'):
+    """How far a mesh lies from the depth the renderer sees (beyond the reference, which has no mesh export): the mesh is
+    rasterised into every pose [N, 3, >=4] (mesh.render_views, csrc/raster.hip) and its disparity compared with disparities
+    [N, H, W] (what prepare.render_disparities returns for the same poses).  Per view and in summary (summarise(...)):
+    coverage, the share of the pixels the mesh covers; depth_l1 / depth_l2, img2l1 / img2mse of the two disparities over the
+    covered pixels (None where the mesh covers none); with masks [N, H, W] bool also coverage_masked (the share of the mask's
+    pixels covered; None for an empty mask) and depth_l1_masked / depth_l2_masked over the covered pixels of the mask."""
+    from . import mesh as mesh_mod
+    H, W = int(hwf[0]), int(hwf[1])
+    dev = mesh.verts.device
+    poses = torch.as_tensor(poses)
+    if poses.dim() != 3 or poses.shape[1] < 3 or poses.shape[2] < 4:
+        raise ValueError(f'mesh_depth_metrics: poses [N, 3, 4] expected, got {tuple(poses.shape)}')
+    N = poses.shape[0]
+    for name, t in (('disparities', disparities), ('masks', masks)):
+        if t is not None and tuple(t.shape) != (N, H, W):
+            raise ValueError(f'mesh_depth_metrics: {name} {tuple(t.shape)} for {N} views of {H} x {W}')
+    target = torch.as_tensor(disparities).to(dev).float()
+    disp, face, _ = mesh_mod.render_views(mesh, hwf, poses, near=near, cull=cull, colors=False)
+    covered = face >= 0
+    per_view = {'coverage': [], 'depth_l1': [], 'depth_l2': []}
+    if masks is not None:
+        masks = torch.as_tensor(masks).to(dev).bool()
+        per_view.update(coverage_masked=[], depth_l1_masked=[], depth_l2_masked=[])
+
+    def both(sel, n):
+        if not bool(sel.any()):
+            return None, None
+        return float(img2l1(disp[n][sel], target[n][sel])), float(img2mse(disp[n][sel], target[n][sel]))
+
+    for n in range(N):
+        per_view['coverage'].append(int(covered[n].sum()) / (H * W))
+        l1, l2 = both(covered[n], n)
+        per_view['depth_l1'].append(l1)
+        per_view['depth_l2'].append(l2)
+        if masks is not None:
+            m = masks[n]
+            per_view['coverage_masked'].append(int((covered[n] & m).sum()) / int(m.sum()) if bool(m.any()) else None)
+            l1, l2 = both(covered[n] & m, n)
+            per_view['depth_l1_masked'].append(l1)
+            per_view['depth_l2_masked'].append(l2)
+    return summarise(per_view)
+
+
 def evaluate_folders(pred_dir, gt_dir, mask_dir=None, device=None):
     """The metrics of the images of pred_dir against those of gt_dir (8-bit, read with load_llff._imread, / 255), paired by
     sorted name (pair_names: a name without a partner is an error); mask_dir: one mask per pair (non-zero = masked).  Returns

@@ -8,6 +8,8 @@ rendered depth maps of the views fused into a truncated signed distance field (c
 smooth() / simplify() / vertex_normals() clean the raw marching-cubes output up (csrc/mesh_ops.hip): Taubin smoothing
 against the lattice staircase, vertex clustering to a tenth of the triangles, and normals from the faces alone for a mesh
 that no longer sits on its lattice.
+render_views() / visible_faces() / keep_faces() look at a mesh through the cameras again (csrc/raster.hip): the disparity,
+face-id and colour maps it presents to each view, the faces any view sees, and the mesh of those alone.
 
 Conventions (shared with csrc/mcubes.hip and the test restatement tests/mc_numpy.py): grid [nx, ny, nz], z fastest; point
 (i, j, k) sits at bmin + (i, j, k) * (bmax - bmin) / (n - 1), in fp32 arithmetic; a corner is inside iff sigma >= threshold
@@ -518,6 +520,47 @@ def simplify(mesh, cell, placement='quadric', dedupe=False, origin=None):
     cycle), which can break that balance."""
     verts, faces, colors, _ = ops.mesh_cluster(mesh.verts, mesh.faces, mesh.colors, origin, cell, placement, dedupe)
     return Mesh(verts, faces, ops.mesh_vertex_normals(verts, faces), colors)
+
+
+def _view_poses(poses, device):
+    return torch.as_tensor(poses).to(device=device, dtype=torch.float32)[:, :3, :4].contiguous()
+
+
+def render_views(mesh, hwf, poses, near=1e-3, cull='none', colors=True):
+    """(disp [V, H, W] fp32, face [V, H, W] int32, rgb [V, H, W, 3] uint8 or None) of `mesh` rasterised into the cameras poses
+    [V, 3, >=4] (ops.mesh_rasterize, csrc/raster.hip; hwf = (H, W, focal)): the inverse of prepare.render_disparities, in its
+    conventions, so the maps compare pixel by pixel with the field's own renders.  disp is 0 and face -1 where the mesh does
+    not cover the pixel.  rgb interpolates mesh.colors (None with colors=False or a mesh without colours).  cull='back' drops
+    the faces seen from inside.  There is no near-plane clipping: a face with a vertex nearer than `near` is dropped whole."""
+    c = mesh.colors if colors else None
+    return ops.mesh_rasterize(mesh.verts, mesh.faces, _view_poses(poses, mesh.verts.device), int(hwf[0]), int(hwf[1]),
+                              float(hwf[2]), near=near, cull=cull, colors=c)
+
+
+def visible_faces(mesh, hwf, poses, near=1e-3, cull='none', chunk=32):
+    """bool [F] on the mesh's device: the faces that win at least one pixel of at least one of the views poses [V, 3, >=4]
+    (render_views, `chunk` views at a time).  Interior sheets and back shells of a sigma level set win none."""
+    F = int(mesh.faces.shape[0])
+    seen = torch.zeros(F, device=mesh.verts.device, dtype=torch.bool)
+    poses = _view_poses(poses, mesh.verts.device)
+    for s in range(0, poses.shape[0], max(1, int(chunk))):
+        face = render_views(mesh, hwf, poses[s:s + int(chunk)], near, cull, colors=False)[1]
+        seen[face[face >= 0].to(torch.int64)] = True
+    return seen
+
+
+def keep_faces(mesh, keep):
+    """The mesh with only the faces keep [F] bool marks (torch plumbing): the faces keep their order, the vertices no kept face
+    references are dropped and the others keep theirs, normals and colours are carried over."""
+    keep = torch.as_tensor(keep, device=mesh.faces.device)
+    if keep.dtype != torch.bool or tuple(keep.shape) != (mesh.faces.shape[0],):
+        raise ValueError(f'keep_faces: keep must be bool [{mesh.faces.shape[0]}], got {keep.dtype} {tuple(keep.shape)}')
+    faces = mesh.faces[keep]
+    used = torch.zeros(mesh.verts.shape[0], device=mesh.verts.device, dtype=torch.bool)
+    used[faces.reshape(-1).to(torch.int64)] = True
+    new = (torch.cumsum(used, 0) - 1).to(torch.int32)
+    pick = lambda a: None if a is None else a[used].contiguous()
+    return Mesh(pick(mesh.verts), new[faces.to(torch.int64)].contiguous(), pick(mesh.normals), pick(mesh.colors))
 
 
 def frustum_bounds(poses, hwf, near, far):

@@ -2703,3 +2703,63 @@ def mesh_cluster(verts, faces, colors, origin, cell, placement='quadric', dedupe
          ptr(crank, _I32), V, F2, V2, ptr(cov, _I32), ptr(out_v) if V2 else none, ptr(out_c, torch.uint8) if V2 else none,
          ptr(out_f, _I32) if F2 else none, st)
     return out_v, out_f, out_c, cov
+
+
+# mesh rasterisation: disparity, face ids and colours per view (beyond the reference, csrc/raster.hip) -------------------------------
+# The definition is csrc/raster.hip's and tests/raster_numpy.py's.  There is no CPU path.
+
+RASTER_CULLS = ('none', 'back')
+RASTER_MAX_SIDE = 16384
+
+
+def mesh_rasterize(verts, faces, poses, H, W, focal, near=1e-3, cull='none', colors=None, stats=False):
+    """Rasterise an indexed mesh into V cameras: (disp [V, H, W] fp32, face [V, H, W] int32, rgb [V, H, W, 3] uint8 or None).
+    verts [Nv, 3] fp32, faces [F, 3] int32 (counter-clockwise seen from outside), poses [V, 3, 4] fp32 camera-to-world, colors
+    [Nv, 3] uint8 or None, all on the GPU; the camera conventions are tsdf_fuse's (looking down -z, no half-pixel offset).  disp
+    is 1 / planar depth of the nearest face at the pixel centre and 0 where nothing covers it, face the index of that face and
+    -1, rgb the perspective-correct interpolation of its vertex colours and 0.  8 sub-pixel bits and the top-left fill rule: two
+    faces that share an edge never both cover a pixel and never both miss it; equal disparities go to the lower face index,
+    so the result does not depend on the order of the atomics and a call equals its repetition bit for bit.  cull='back' drops
+    the faces seen from inside.  THERE IS NO NEAR-PLANE CLIPPING: a face with a vertex nearer than `near` (or behind the
+    camera, or more than 16,384 pixels off the image centre's axes) is dropped whole for that view.  H, W in 1..16384; focal
+    and near finite and > 0.  V = 0, F = 0 and Nv = 0 give empty maps.  ValueError for bad shapes or dtypes, CPU tensors, or a
+    face index outside [0, Nv) (checked on the device, one flag read back: the only synchronisation).  stats=True appends
+    (fragments, atomics sent) as a [2] int64 device tensor, from a counting variant of the fragment kernel.  Two launches and
+    one clear.  Detached."""
+    import math
+    what = 'mesh_rasterize'
+    v, f, *rest = _mesh_operands(what, verts, faces, colors)
+    c = rest[0] if rest else None
+    p = _pose_batch(what, poses, 'poses')
+    if not p.is_cuda:
+        raise ValueError(f'{what}: tensors on the GPU expected (the HIP path has no CPU path)')
+    if p.device != v.device:
+        raise ValueError(f'{what}: tensors on one device expected, got {sorted({str(v.device), str(p.device)})}')
+    if not p.is_contiguous():
+        raise ValueError(f'{what}: every operand must be contiguous')
+    if int(H) != H or int(W) != W or not (1 <= int(H) <= RASTER_MAX_SIDE and 1 <= int(W) <= RASTER_MAX_SIDE):
+        raise ValueError(f'{what}: H and W must be integers in 1..{RASTER_MAX_SIDE}, got {H!r} x {W!r}')
+    H, W, focal, near = int(H), int(W), float(focal), float(near)
+    if not (math.isfinite(focal) and focal > 0 and math.isfinite(near) and near > 0):
+        raise ValueError(f'{what}: focal {focal} and near {near} must be finite and > 0')
+    if cull not in RASTER_CULLS:
+        raise ValueError(f'{what}: cull must be one of {RASTER_CULLS}, got {cull!r}')
+    Nv, F, V = int(v.shape[0]), int(f.shape[0]), int(p.shape[0])
+    dev = v.device
+    disp = torch.empty((V, H, W), device=dev, dtype=_F32)
+    face = torch.empty((V, H, W), device=dev, dtype=_I32)
+    rgb = torch.empty((V, H, W, 3), device=dev, dtype=torch.uint8) if c is not None else None
+    keys = torch.empty((V, H, W), device=dev, dtype=torch.int64)
+    flag = torch.empty(1, device=dev, dtype=_I32)
+    counts = torch.empty(2, device=dev, dtype=torch.int64) if stats else None
+    none = ptr(None)
+    args = (ptr(v) if Nv else none, ptr(f, _I32) if F else none)
+    geom = (Nv, F, ptr(p) if V else none, V, H, W, focal, near)
+    call('mvip_raster_fragments', *args, *geom, RASTER_CULLS.index(cull), ptr(keys, torch.int64) if V else none, ptr(flag, _I32),
+         ptr(counts, torch.int64) if stats else none, stream())
+    call('mvip_raster_resolve', ptr(keys, torch.int64) if V else none, *args, ptr(c, torch.uint8) if c is not None and Nv else none,
+         *geom, ptr(disp) if V else none, ptr(face, _I32) if V else none, ptr(rgb, torch.uint8) if c is not None and V else none,
+         stream())
+    if int(flag.cpu()):
+        raise ValueError(f'{what}: a face index lies outside [0, {Nv})')
+    return (disp, face, rgb, counts) if stats else (disp, face, rgb)

@@ -5,6 +5,7 @@ binary PLY (mvip_nerf_amd/mesh.py).  Prints sigma percentiles of the grid (to ch
   python tools/extract_mesh.py CKPT.tar --out mesh.ply [--model mlp|tcnn] [--bound-min x y z --bound-max x y z]
          [--resolution 256] [--threshold 10] [--network fine|coarse] [--precision fp32|split] [--no-colors]
          [--keep-largest K] [--min-component N] [--smooth ITERS] [--simplify STEPS] [--simplify-placement quadric|mean]
+         [--drop-unseen --datadir SCENE [--factor 4]]
   python tools/extract_mesh.py --tsdf --fixture [--iters 1500] --out mesh.ply [--trunc T] [--view-step S] ...
   python tools/extract_mesh.py --tsdf CKPT.tar --datadir SCENE [--factor 4] --out mesh.ply [--trunc T] [--view-step S] ...
 
@@ -17,6 +18,11 @@ clusters its vertices in cubic cells of STEPS times the largest lattice step (me
 mean; 0, the default: off).  Both come after the floater options and recompute the normals from the faces; the colours are
 those of the extracted vertices (averaged per cluster).  The triangle and vertex counts before and after are printed.
 Without the two flags the file is what it was.
+
+--drop-unseen rasterises the finished mesh into the training cameras (mesh.visible_faces, csrc/raster.hip) and writes only
+the faces that win a pixel in at least one of them, with the vertices those faces use: the interior sheets and back shells
+of a sigma level set go.  It comes last, after the clean-up.  The cameras are those of --tsdf; without --tsdf they are read
+from --datadir / --factor.  Without the flag the file is what it was.
 
 --tsdf meshes what the renderer sees instead of thresholding sigma (mesh.fuse_depths): the disparity of every view (every
 S-th with --view-step S) is rendered and fused into a truncated signed distance field whose zero level set is extracted
@@ -89,6 +95,16 @@ def clean_up(a, m, lo, hi, res):
     return out, t
 
 
+def drop_unseen(a, m, hwf, poses):
+    """--drop-unseen on the finished Mesh m: (mesh, seconds)."""
+    if not a.drop_unseen:
+        return m, 0.0
+    out, t = _timed(lambda: mesh.keep_faces(m, mesh.visible_faces(m, hwf, poses)))
+    print(f'visible from {poses.shape[0]} views of {int(hwf[0])} x {int(hwf[1])}: {m.faces.shape[0]} triangles, {m.verts.shape[0]} vertices '
+          f'-> {out.faces.shape[0]} triangles, {out.verts.shape[0]} vertices')
+    return out, t
+
+
 def main_tsdf(ap, a, res, dev):
     """--tsdf: render the views' disparities, fuse them, extract the zero level set over the observed cells."""
     from mvip_nerf_amd import prepare
@@ -125,10 +141,12 @@ def main_tsdf(ap, a, res, dev):
     (verts, faces, normals), t_mc = _timed(lambda: mesh.marching_cubes(g, 1.0, lo32, hi32, valid=valid))
     colors, t_col = (None, 0.0) if a.no_colors else _timed(lambda: mesh.vertex_colors(te, verts, normals, a.network))
     m, t_clean = clean_up(a, mesh.Mesh(verts, faces, normals, colors), lo32, hi32, res)
+    m, t_seen = drop_unseen(a, m, hwf, poses)
     _, t_ply = _timed(lambda: mesh.save_ply(a.out, m))
     print(f'tsdf zero level set: {m.verts.shape[0]} vertices, {m.faces.shape[0]} triangles -> {a.out}')
     print(f'time  model {t_model * 1e3:.1f} ms  render {t_render * 1e3:.1f} ms  fusion {t_fuse * 1e3:.1f} ms  components {t_cc * 1e3:.1f} ms  '
-          f'marching cubes {t_mc * 1e3:.1f} ms  colours {t_col * 1e3:.1f} ms  clean-up {t_clean * 1e3:.1f} ms  write {t_ply * 1e3:.1f} ms')
+          f'marching cubes {t_mc * 1e3:.1f} ms  colours {t_col * 1e3:.1f} ms  clean-up {t_clean * 1e3:.1f} ms  '
+          + (f'visibility {t_seen * 1e3:.1f} ms  ' if a.drop_unseen else '') + f'write {t_ply * 1e3:.1f} ms')
     return 0
 
 
@@ -150,10 +168,12 @@ def main(argv=None):
     ap.add_argument('--simplify', type=float, default=0.0, metavar='STEPS',
                     help='cluster the vertices in cells of STEPS times the largest lattice step (0: off)')
     ap.add_argument('--simplify-placement', choices=('quadric', 'mean'), default='quadric')
+    ap.add_argument('--drop-unseen', action='store_true',
+                    help='write only the faces some training view sees (cameras: those of --tsdf, else --datadir / --factor)')
     ap.add_argument('--tsdf', action='store_true', help='fuse rendered depth maps instead of thresholding sigma')
     ap.add_argument('--fixture', action='store_true', help='--tsdf: train the scene-1 fixture and use its cameras')
     ap.add_argument('--iters', type=int, default=1500, help='training iterations of --fixture')
-    ap.add_argument('--datadir', help='--tsdf with a checkpoint: the scene whose cameras are rendered')
+    ap.add_argument('--datadir', help='--tsdf with a checkpoint: the scene whose cameras are rendered; --drop-unseen: its cameras')
     ap.add_argument('--factor', type=int, default=4)
     ap.add_argument('--trunc', type=float, default=None, help='--tsdf: truncation distance (default: 4 lattice steps)')
     ap.add_argument('--view-step', type=int, default=1, metavar='S', help='--tsdf: fuse every S-th view')
@@ -164,8 +184,8 @@ def main(argv=None):
     dev = torch.device('cuda', 0)
     if a.tsdf:
         return main_tsdf(ap, a, res, dev)
-    if a.fixture or a.datadir or a.ckpt is None:
-        ap.error('a checkpoint is required; --fixture / --datadir belong to --tsdf')
+    if a.fixture or a.ckpt is None or bool(a.datadir) != a.drop_unseen:
+        ap.error('a checkpoint is required; --fixture belongs to --tsdf, --datadir to --tsdf or --drop-unseen (which needs it)')
     a.bound_min = (-1.0, -1.0, -1.0) if a.bound_min is None else a.bound_min
     a.bound_max = (1.0, 1.0, 1.0) if a.bound_max is None else a.bound_max
     kw, step = load_model(a.ckpt, a.model, dev)
@@ -194,10 +214,15 @@ def main(argv=None):
     (verts, faces, normals), t_mc = timed(lambda: mesh.marching_cubes(grid, a.threshold, a.bound_min, a.bound_max))
     colors, t_col = (None, 0.0) if a.no_colors else timed(lambda: mesh.vertex_colors(kw, verts, normals, a.network))
     m, t_clean = clean_up(a, mesh.Mesh(verts, faces, normals, colors), a.bound_min, a.bound_max, res)
+    t_seen = 0.0
+    if a.drop_unseen:
+        from mvip_nerf_amd.load_llff import load_llff_data
+        cams = load_llff_data(a.datadir, factor=a.factor)[1]
+        m, t_seen = drop_unseen(a, m, tuple(float(v) for v in cams[0, :3, -1]), torch.from_numpy(cams[:, :3, :4].copy()).to(dev))
     _, t_ply = timed(lambda: mesh.save_ply(a.out, m))
     print(f'threshold {a.threshold}: {m.verts.shape[0]} vertices, {m.faces.shape[0]} triangles -> {a.out}')
     print(f'time  density grid {t_grid * 1e3:.1f} ms  components {t_cc * 1e3:.1f} ms  marching cubes {t_mc * 1e3:.1f} ms  colours {t_col * 1e3:.1f} ms  '
-          f'clean-up {t_clean * 1e3:.1f} ms  write {t_ply * 1e3:.1f} ms')
+          f'clean-up {t_clean * 1e3:.1f} ms  ' + (f'visibility {t_seen * 1e3:.1f} ms  ' if a.drop_unseen else '') + f'write {t_ply * 1e3:.1f} ms')
     return 0
 
 
