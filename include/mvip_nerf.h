@@ -1059,6 +1059,40 @@ int mvip_raster_resolve(const void *keys, const float *verts, const int *faces, 
                         int64_t n_faces, const float *poses, int64_t n_views, int H, int W, double focal, double znear,
                         float *disp, int *face, void *rgb, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mesh texturing: colours for the points of a mesh baked from the views it was built from, a per-face texture atlas, and the
+ * textured mesh rendered back into a camera (beyond the reference: no entry point has a reference call site; csrc/texture.hip,
+ * ops.mesh_bake_points / mesh_bake_atlas / mesh_texture_resolve, mesh.bake_texture / colors_from_views / render_textured).
+ * The definition, in fp64 and integers with its operation order, is written out in csrc/texture.hip and
+ * tests/texture_numpy.py: the cameras and the projection of mvip_raster_* (one definition, csrc/raster_device.h); a view
+ * contributes to a point iff the point projects inside the image at z >= znear, faces the camera (cull 1: nrm . (o - p) > 0,
+ * cull 0: != 0) and the rasterised disparity D of the same mesh satisfies |D z - 1| <= tol at all four pixels of the bilinear
+ * footprint (and masks, if not NULL, is non-zero there); weight = cos^2 of incidence; mode 0 blends by weight, mode 1 takes the
+ * view of largest weight.  The atlas: faces 2k and 2k + 1 share a block of (texels + 3)^2 texels, blocks row-major,
+ * ceil(sqrt(ceil(F / 2))) per row.  All operands DEVICE memory, dense: images [V,H,W,3] bytes, disp [V,H,W] fp32, masks
+ * [V,H,W] bytes or NULL, poses [V,3,4] fp32, verts [Nv,3] fp32, faces [F,3] int32.  Outputs per sample point: rgb 3 bytes,
+ * wsum fp32 (the sum of the weights; 0 = no view), best int32 (the view of largest weight or -1).  MVIP_EINVAL before any
+ * device call for: a negative count, a count > 2^31 - 1 (3 F for faces), H or W outside 1..16384, texels outside 1..32, a
+ * texture side over 16,384, focal or znear not finite and > 0, tol not finite or < 0, cull, mode or order not 0 or 1, a NULL
+ * operand that a non-zero count makes necessary.  N = 0, F = 0, V = 0 are valid.  Every launch on the caller's stream.
+ * mvip_texture_bake_points: points, normals [N,3] fp32 -> rgb [N,3], wsum [N], best [N].
+ * mvip_texture_bake_atlas: one sample point per texel of the atlas [Ht,Wt] of (F, texels), derived from the texel index;
+ *   rgb [Ht,Wt,3], wsum [Ht,Wt], best [Ht,Wt]; texels without an owner hold 0 / 0 / -1.  order: how texels map to lanes
+ *   (0 texture row-major, 1 block-major), the same output.  flag[0] is cleared, then set to 1 iff a face index lies outside
+ *   [0, Nv) (the texels of such a face hold 0 / 0 / -1).
+ * mvip_texture_resolve: face [V,H,W] int32 of mvip_raster_resolve for the same mesh, poses and camera -> rgb [V,H,W,3]: the
+ *   bilinear value of atlas [Ht,Wt,3] at the winner's perspective-correct barycentrics, 0 where face < 0 or >= F. */
+int mvip_texture_bake_points(const float *points, const float *normals, int64_t n_points, const void *images, const float *disp,
+                             const void *masks, const float *poses, int64_t n_views, int H, int W, double focal, double znear,
+                             double tol, int cull, int mode, void *rgb, float *wsum, int *best, void *stream);
+int mvip_texture_bake_atlas(const float *verts, const int *faces, int64_t n_verts, int64_t n_faces, int texels, int order,
+                            const void *images, const float *disp, const void *masks, const float *poses, int64_t n_views, int H,
+                            int W, double focal, double znear, double tol, int cull, int mode, void *rgb, float *wsum, int *best,
+                            int *flag, void *stream);
+int mvip_texture_resolve(const int *face, const float *verts, const int *faces, int64_t n_verts, int64_t n_faces,
+                         const void *atlas, int texels, const float *poses, int64_t n_views, int H, int W, double focal,
+                         double znear, void *rgb, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -221,6 +221,12 @@ _SIGNATURES = {
                                      _c_f, _c_f, _c_f]),
     'mvip_raster_resolve': (_int, [_c_f, _c_f, _c_f, _c_f, _i64, _i64, _c_f, _i64, _int, _int, ctypes.c_double, ctypes.c_double,
                                    _c_f, _c_f, _c_f, _c_f]),
+    'mvip_texture_bake_points': (_int, [_c_f, _c_f, _i64, _c_f, _c_f, _c_f, _c_f, _i64, _int, _int, ctypes.c_double, ctypes.c_double,
+                                        ctypes.c_double, _int, _int, _c_f, _c_f, _c_f, _c_f]),
+    'mvip_texture_bake_atlas': (_int, [_c_f, _c_f, _i64, _i64, _int, _int, _c_f, _c_f, _c_f, _c_f, _i64, _int, _int, ctypes.c_double,
+                                       ctypes.c_double, ctypes.c_double, _int, _int, _c_f, _c_f, _c_f, _c_f, _c_f]),
+    'mvip_texture_resolve': (_int, [_c_f, _c_f, _c_f, _i64, _i64, _c_f, _int, _c_f, _i64, _int, _int, ctypes.c_double, ctypes.c_double,
+                                    _c_f, _c_f]),
 }
 
 # every symbol include/mvip_nerf.h declares; tests check the built library exports all of them

@@ -206,6 +206,51 @@ def mesh_depth_metrics(mesh, hwf, poses, disparities, masks=None, near=1e-3, cul
     return summarise(per_view)
 
 
+def mesh_image_metrics(mesh, texture, hwf, poses, images, masks=None, near=1e-3, cull='none'):
+    """How the exported mesh LOOKS next to images [N, H, W, 3] (uint8, or floats in 0..1) of the cameras poses [N, 3, >=4]
+    (beyond the reference, which has no mesh export): the mesh is rendered with `texture` (mesh.render_textured; a
+    mesh.Texture) or, with texture None, with its vertex colours (mesh.render_views).  Per view and in summary
+    (summarise(...)): coverage, the share of the pixels the mesh covers (of the mask's pixels with masks [N, H, W] bool, which
+    then also restricts everything below); psnr over the covered pixels; ssim = ops.ssim with the covered pixels as its mask
+    (None for images under 11 x 11).  None where the mesh covers nothing."""
+    from . import mesh as mesh_mod, ops
+    H, W = int(hwf[0]), int(hwf[1])
+    dev = mesh.verts.device
+    poses = torch.as_tensor(poses)
+    if poses.dim() != 3 or poses.shape[1] < 3 or poses.shape[2] < 4:
+        raise ValueError(f'mesh_image_metrics: poses [N, 3, 4] expected, got {tuple(poses.shape)}')
+    N = poses.shape[0]
+    images = torch.as_tensor(images)
+    if tuple(images.shape) != (N, H, W, 3):
+        raise ValueError(f'mesh_image_metrics: images {tuple(images.shape)} for {N} views of {H} x {W}')
+    if masks is not None and tuple(masks.shape) != (N, H, W):
+        raise ValueError(f'mesh_image_metrics: masks {tuple(masks.shape)} for {N} views of {H} x {W}')
+    if texture is None:
+        if mesh.colors is None:
+            raise ValueError('mesh_image_metrics: a mesh without colours needs a texture')
+        _, face, rgb = mesh_mod.render_views(mesh, hwf, poses, near=near, cull=cull)
+    else:
+        _, face, rgb = mesh_mod.render_textured(mesh, texture, hwf, poses, near=near, cull=cull)
+    covered = face >= 0
+    region = None
+    if masks is not None:
+        region = torch.as_tensor(masks).to(dev).bool()
+        covered = covered & region
+    pred = rgb.float() / 255.0
+    gt = images.to(dev)
+    gt = (gt.float() / 255.0 if gt.dtype == torch.uint8 else gt.float()).contiguous()
+    big = H >= SSIM_MIN_SIDE and W >= SSIM_MIN_SIDE
+    ssim = ops.ssim(pred.contiguous(), gt, mask=covered.contiguous()).cpu().tolist() if big and N else [None] * N
+    per_view = {'coverage': [], 'psnr': [], 'ssim': []}
+    for n in range(N):
+        total = int(region[n].sum()) if region is not None else H * W
+        hit = int(covered[n].sum())
+        per_view['coverage'].append(hit / total if total else None)
+        per_view['psnr'].append(_psnr(img2mse(pred[n][covered[n]], gt[n][covered[n]])) if hit else None)
+        per_view['ssim'].append(ssim[n] if hit else None)
+    return summarise(per_view)
+
+
 def evaluate_folders(pred_dir, gt_dir, mask_dir=None, device=None):
     """The metrics of the images of pred_dir against those of gt_dir (8-bit, read with load_llff._imread, / 255), paired by
     sorted name (pair_names: a name without a partner is an error); mask_dir: one mask per pair (non-zero = masked).  Returns

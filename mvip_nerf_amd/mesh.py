@@ -10,6 +10,9 @@ against the lattice staircase, vertex clustering to a tenth of the triangles, an
 that no longer sits on its lattice.
 render_views() / visible_faces() / keep_faces() look at a mesh through the cameras again (csrc/raster.hip): the disparity,
 face-id and colour maps it presents to each view, the faces any view sees, and the mesh of those alone.
+bake_texture() / colors_from_views() / render_textured() / save_obj() take the colour from the views instead of the field
+(csrc/texture.hip): a per-face texture atlas or vertex colours blended from the images of the cameras that see each point,
+the textured mesh rendered back into a camera, and OBJ + MTL + PNG export.
 
 Conventions (shared with csrc/mcubes.hip and the test restatement tests/mc_numpy.py): grid [nx, ny, nz], z fastest; point
 (i, j, k) sits at bmin + (i, j, k) * (bmax - bmin) / (n - 1), in fp32 arithmetic; a corner is inside iff sigma >= threshold
@@ -19,6 +22,7 @@ signed volume.  Normals are -grad sigma (central differences), normalised.
 """
 import collections
 import math
+import os
 
 import numpy as np
 import torch
@@ -563,6 +567,135 @@ def keep_faces(mesh, keep):
     return Mesh(pick(mesh.verts), new[faces.to(torch.int64)].contiguous(), pick(mesh.normals), pick(mesh.colors))
 
 
+Texture = collections.namedtuple('Texture', ['image', 'uv', 'seen', 'texels'])
+
+
+def atlas_layout(n_faces, texels):
+    """((Ht, Wt, 3), uv [F, 3, 2] fp32 numpy): the shape of the texture atlas of a mesh of n_faces faces at `texels` texels along a
+    face's leg (1..32) and the texture coordinates of every face corner in OBJ convention, u = x / Wt, v = 1 - y / Ht of the
+    continuous texel position (texel centres at integer + 1/2).  The layout is csrc/texture.hip's, a pure integer function of
+    (F, texels): faces 2k and 2k + 1 share block k of side S = texels + 3, the blocks lie row-major, ceil(sqrt(ceil(F / 2))) per
+    row; face 2k has its corners at (1/2, 1/2), (texels + 1/2, 1/2), (1/2, texels + 1/2) of the block, face 2k + 1 the same
+    reflected through the block's centre.  A bilinear lookup inside a face's UV triangle reads only texels that face owns.
+    ValueError for texels outside 1..32 or a texture side over 16,384.  Host code."""
+    Ht, Wt, Bx, _, S = ops.texture_layout(n_faces, texels)
+    F, n = int(n_faces), int(texels)
+    f = np.arange(F, dtype=np.int64)
+    k = f // 2
+    by, bx = k // max(Bx, 1), k % max(Bx, 1)
+    upper = (f % 2 == 1)[:, None]
+    a, b = np.array([0.0, n, 0.0])[None], np.array([0.0, 0.0, n])[None]
+    x = np.where(upper, ((bx + 1) * S)[:, None] - 0.5 - a, (bx * S)[:, None] + 0.5 + a)
+    y = np.where(upper, ((by + 1) * S)[:, None] - 0.5 - b, (by * S)[:, None] + 0.5 + b)
+    uv = np.stack([x / float(max(Wt, 1)), 1.0 - y / float(max(Ht, 1))], -1).astype(np.float32)
+    return (Ht, Wt, 3), uv
+
+
+def _texel_points(mesh, texels, idx):
+    """(points, unit normals) [K, 3] fp32 of the texels idx [K] (flat y * Wt + x, all owned) of the atlas of `mesh`, in torch on
+    the mesh's device: the sample points of csrc/texture.hip rounded to fp32, for the field query of bake_texture."""
+    F = int(mesh.faces.shape[0])
+    _, Wt, Bx, _, S = ops.texture_layout(F, texels)
+    n = int(texels)
+    Y, X = idx // Wt, idx % Wt
+    bx, by = X // S, Y // S
+    i, j = X - bx * S, Y - by * S
+    upper = i + j > S - 1
+    face = 2 * (by * Bx + bx) + upper.to(torch.int64)
+    i, j = torch.where(upper, S - 1 - i, i), torch.where(upper, S - 1 - j, j)
+    inner = i + j < n
+    m = (i - j + n).clamp(0, 2 * n)
+    l1 = torch.where(inner, i.double() / n, m.double() / (2 * n))
+    l2 = torch.where(inner, j.double() / n, (2 * n - m).double() / (2 * n))
+    l0 = torch.where(inner, (1.0 - l1) - l2, torch.zeros_like(l1))
+    fv = mesh.verts.double()[mesh.faces.to(torch.int64)[face]]                          # [K, 3, 3]
+    p = (l0[:, None] * fv[:, 0] + l1[:, None] * fv[:, 1]) + l2[:, None] * fv[:, 2]
+    nrm = torch.cross(fv[:, 1] - fv[:, 0], fv[:, 2] - fv[:, 0], dim=-1)
+    nrm = nrm / nrm.norm(dim=-1, keepdim=True).clamp_min(1e-300)
+    return p.float().contiguous(), nrm.float().contiguous()
+
+
+def _byte_images(images, device):
+    """images [V, H, W, 3] as uint8 on `device`: uint8 as it is, floats in 0..1 by floor(255 x + 1/2) clamped."""
+    im = torch.as_tensor(images).to(device)
+    if im.dtype != torch.uint8:
+        im = (im.float() * 255.0 + 0.5).floor().clamp(0, 255).to(torch.uint8)
+    return im.contiguous()
+
+
+def bake_texture(mesh, hwf, poses, images, texels=8, near=1e-3, tol=0.05, cull='back', mode='blend', masks=None, render_kwargs=None,
+                 network='fine', chunk=1 << 18, verbose=True):
+    """Texture(image [Ht, Wt, 3] uint8, uv [F, 3, 2] fp32 numpy, seen [Ht, Wt] bool, texels) of `mesh` baked from images [V, H, W, 3]
+    (uint8, or floats in 0..1) of the cameras poses [V, 3, >=4], hwf = (H, W, focal): the mesh is rasterised into the views for
+    its own disparities (render_views, cull off: a back face occludes too), then ops.mesh_bake_atlas blends per texel the views
+    that see it (csrc/texture.hip; atlas_layout for the layout).  seen = a view contributed (wsum > 0).  Texels no view sees
+    hold 0, or with render_kwargs the field's colour at the texel's point seen head-on (view direction = -face normal, the rule
+    of vertex_colors, `chunk` points at a time).  Prints the unseen share of the owned texels (verbose)."""
+    dev = mesh.verts.device
+    H, W, focal = int(hwf[0]), int(hwf[1]), float(hwf[2])
+    p = _view_poses(poses, dev)
+    im = _byte_images(images, dev)
+    m = None if masks is None else torch.as_tensor(masks).to(dev).bool().contiguous()
+    disp = ops.mesh_rasterize(mesh.verts, mesh.faces, p, H, W, focal, near=near, cull='none')[0]
+    rgb, wsum, best = ops.mesh_bake_atlas(mesh.verts, mesh.faces, texels, im, disp, p, focal, near=near, tol=tol, cull=cull, mode=mode,
+                                          masks=m)
+    seen = wsum > 0
+    F = int(mesh.faces.shape[0])
+    Ht, Wt, Bx, _, S = ops.texture_layout(F, texels)
+    owned = _owned_texels(F, texels, dev)
+    unseen = owned & ~seen
+    n_owned, n_unseen = int(owned.sum()), int(unseen.sum())
+    if render_kwargs is not None and n_unseen:
+        net = _network(render_kwargs, network)
+        idx = torch.nonzero(unseen.reshape(-1)).reshape(-1)
+        flat = rgb.reshape(-1, 3)
+        with torch.no_grad():
+            for s in range(0, idx.shape[0], int(chunk)):
+                pts, nrm = _texel_points(mesh, texels, idx[s:s + int(chunk)])
+                raw = _query(render_kwargs, net, pts, -nrm)
+                flat[idx[s:s + int(chunk)]] = (torch.sigmoid(raw[:, :3]) * 255.0 + 0.5).clamp(0, 255).to(torch.uint8)
+    if verbose:
+        print(f'texture {Ht} x {Wt} at {int(texels)} texels per leg: {n_owned} owned texels, {n_unseen} seen by no view '
+              f'({n_unseen / max(n_owned, 1):.4f})' + (', filled from the field' if render_kwargs is not None and n_unseen else ''))
+    return Texture(rgb, atlas_layout(F, texels)[1], seen, int(texels))
+
+
+def _owned_texels(n_faces, texels, device):
+    """bool [Ht, Wt]: the texels of the atlas that a face owns."""
+    Ht, Wt, Bx, _, S = ops.texture_layout(n_faces, texels)
+    Y, X = torch.meshgrid(torch.arange(Ht, device=device), torch.arange(Wt, device=device), indexing='ij')
+    bx, by = X // S, Y // S
+    upper = (X - bx * S) + (Y - by * S) > S - 1
+    return 2 * (by * Bx + bx) + upper.to(torch.int64) < int(n_faces)
+
+
+def colors_from_views(mesh, hwf, poses, images, near=1e-3, tol=0.05, cull='back', mode='blend', masks=None):
+    """A Mesh whose vertex colours are baked from the views at the vertices with mesh.normals (ops.mesh_bake_points; the
+    arguments of bake_texture): the colour the cameras saw where the vertex IS, not the field's answer at a point that smoothing
+    or clustering has moved off its surface.  A vertex that no view sees keeps its old colour (0 for a mesh without colours)."""
+    dev = mesh.verts.device
+    H, W, focal = int(hwf[0]), int(hwf[1]), float(hwf[2])
+    p = _view_poses(poses, dev)
+    m = None if masks is None else torch.as_tensor(masks).to(dev).bool().contiguous()
+    disp = ops.mesh_rasterize(mesh.verts, mesh.faces, p, H, W, focal, near=near, cull='none')[0]
+    rgb, wsum, _ = ops.mesh_bake_points(mesh.verts, mesh.normals.contiguous(), _byte_images(images, dev), disp, p, focal, near=near,
+                                        tol=tol, cull=cull, mode=mode, masks=m)
+    old = mesh.colors if mesh.colors is not None else torch.zeros_like(rgb)
+    return Mesh(mesh.verts, mesh.faces, mesh.normals, torch.where((wsum > 0)[:, None], rgb, old))
+
+
+def render_textured(mesh, texture, hwf, poses, near=1e-3, cull='none'):
+    """(disp [V, H, W] fp32, face [V, H, W] int32, rgb [V, H, W, 3] uint8) of `mesh` with `texture` (bake_texture) in the cameras
+    poses [V, 3, >=4]: render_views for the geometry, ops.mesh_texture_resolve for the colour (the atlas read bilinearly at the
+    perspective-correct position inside the winning face).  rgb is 0 where the mesh does not cover the pixel."""
+    dev = mesh.verts.device
+    p = _view_poses(poses, dev)
+    focal = float(hwf[2])
+    disp, face, _ = ops.mesh_rasterize(mesh.verts, mesh.faces, p, int(hwf[0]), int(hwf[1]), focal, near=near, cull=cull)
+    image = torch.as_tensor(texture.image).to(dev).contiguous()
+    return disp, face, ops.mesh_texture_resolve(face, mesh.verts, mesh.faces, image, texture.texels, p, focal, near=near)
+
+
 def frustum_bounds(poses, hwf, near, far):
     """(bound_min, bound_max) float32 [3] each: the axis-aligned box of every camera's view frustum between near and far.
     poses [N, 3, >=4] camera-to-world (run.py's convention: x right, y up, looking down -z); hwf = (H, W, focal); the
@@ -613,3 +746,43 @@ def save_ply(path, mesh):
         fh.write(('\n'.join(head) + '\n').encode('ascii'))
         fh.write(vert.tobytes())
         fh.write(face.tobytes())
+
+
+def _host(a, dtype):
+    return None if a is None else np.ascontiguousarray(a.detach().cpu().numpy() if torch.is_tensor(a) else a, dtype)
+
+
+def save_obj(path, mesh, texture=None):
+    """Wavefront OBJ of `mesh` (tensors or numpy arrays): `v` and `vn` per vertex and `f` with 1-based indices.  With a Texture
+    (bake_texture) three files: path, <stem>.mtl next to it with `map_Kd <stem>.png`, and <stem>.png (run._write_png; PNG row 0 is
+    the texture's row 0, the flip of v is in texture.uv); one `vt` per face corner and faces `f a/t/n`.  Without a texture only
+    path is written, faces `f a//n`.  Returns the list of the files written."""
+    v, nrm, f = _host(mesh.verts, np.float64), _host(mesh.normals, np.float64), _host(mesh.faces, np.int64)
+    root, _ = os.path.splitext(path)
+    stem = os.path.basename(root)
+    lines = ['# mvip_nerf_amd.mesh']
+    files = [path]
+    if texture is not None:
+        from . import run
+        uv = _host(texture.uv, np.float64)
+        if uv.shape != (f.shape[0], 3, 2):
+            raise ValueError(f'save_obj: texture.uv {uv.shape} for {f.shape[0]} faces')
+        run._write_png(root + '.png', _host(texture.image, np.uint8))
+        with open(root + '.mtl', 'w') as fh:
+            fh.write(f'newmtl {stem}\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd {stem}.png\n')
+        lines += [f'mtllib {stem}.mtl', f'usemtl {stem}']
+        files += [root + '.mtl', root + '.png']
+    lines += [f'v {x:.9g} {y:.9g} {z:.9g}' for x, y, z in v]
+    if nrm is not None:
+        lines += [f'vn {x:.9g} {y:.9g} {z:.9g}' for x, y, z in nrm]
+    if texture is not None:
+        lines += [f'vt {a:.9g} {b:.9g}' for a, b in uv.reshape(-1, 2)]
+    for k, (a, b, c) in enumerate(f + 1):
+        if texture is not None:
+            t = 3 * k + 1
+            lines.append(f'f {a}/{t}/{a} {b}/{t + 1}/{b} {c}/{t + 2}/{c}' if nrm is not None else f'f {a}/{t} {b}/{t + 1} {c}/{t + 2}')
+        else:
+            lines.append(f'f {a}//{a} {b}//{b} {c}//{c}' if nrm is not None else f'f {a} {b} {c}')
+    with open(path, 'w') as fh:
+        fh.write('\n'.join(lines) + '\n')
+    return files

@@ -2763,3 +2763,181 @@ def mesh_rasterize(verts, faces, poses, H, W, focal, near=1e-3, cull='none', col
     if int(flag.cpu()):
         raise ValueError(f'{what}: a face index lies outside [0, {Nv})')
     return (disp, face, rgb, counts) if stats else (disp, face, rgb)
+
+
+# mesh texturing: colours baked from the views, a per-face atlas, the textured render (beyond the reference, csrc/texture.hip) ---------
+# The definition is csrc/texture.hip's and tests/texture_numpy.py's.  There is no CPU path.
+
+TEXTURE_MODES = ('blend', 'best')
+TEXTURE_ORDERS = ('row', 'block')
+TEXTURE_MAX_TEXELS = 32
+
+
+def texture_layout(n_faces, texels):
+    """(Ht, Wt, Bx, By, S) of the atlas of n_faces faces at `texels` texels along a leg: the layout of csrc/texture.hip, in
+    integers.  ValueError for texels outside 1..32 or a texture side over 16,384."""
+    F = int(n_faces)
+    if int(texels) != texels or not 1 <= int(texels) <= TEXTURE_MAX_TEXELS or F < 0:
+        raise ValueError(f'texture_layout: texels must be an integer in 1..{TEXTURE_MAX_TEXELS} and F >= 0, got {texels!r}, {F}')
+    S = int(texels) + 3
+    B = (F + 1) // 2
+    Bx = 0
+    while Bx * Bx < B:
+        Bx += 1
+    By = -(-B // Bx) if Bx else 0
+    if Bx * S > RASTER_MAX_SIDE or By * S > RASTER_MAX_SIDE:
+        raise ValueError(f'texture_layout: {F} faces at {texels} texels need a texture of {By * S} x {Bx * S}: a side over {RASTER_MAX_SIDE}')
+    return By * S, Bx * S, Bx, By, S
+
+
+def _bake_views(what, dev, images, disp, poses, focal, near, tol, cull, mode, masks):
+    """The checks the two bakes share: (images, disp, poses, masks or None, V, H, W, focal, near, tol, cull index, mode index)."""
+    import math
+    d = _image_batch(what, disp, _F32, 'disp')
+    p = _pose_batch(what, poses, 'poses')
+    if not torch.is_tensor(images) or images.dtype != torch.uint8 or images.dim() != 4 or images.shape[-1] != 3:
+        got = f'{tuple(images.shape)} {images.dtype}' if torch.is_tensor(images) else type(images).__name__
+        raise ValueError(f'{what}: images must be a torch.uint8 tensor [V, H, W, 3] on the GPU, got {got}')
+    im = images.detach()
+    tensors = [im, d, p]
+    if masks is not None:
+        tensors.append(_image_batch(what, masks, torch.bool, 'masks'))
+    if not all(t.is_cuda for t in tensors):
+        raise ValueError(f'{what}: tensors on the GPU expected (the HIP path has no CPU path)')
+    if any(t.device != dev for t in tensors):
+        raise ValueError(f'{what}: tensors on one device expected, got {sorted({str(dev)} | {str(t.device) for t in tensors})}')
+    if not all(t.is_contiguous() for t in tensors):
+        raise ValueError(f'{what}: every operand must be contiguous')
+    V, H, W = (int(x) for x in d.shape)
+    if tuple(im.shape) != (V, H, W, 3) or p.shape[0] != V or (masks is not None and tuple(tensors[3].shape) != (V, H, W)):
+        raise ValueError(f'{what}: images {tuple(im.shape)}, disp {tuple(d.shape)}, poses {tuple(p.shape)}'
+                         + (f', masks {tuple(tensors[3].shape)}' if masks is not None else '') + ': one V, H, W expected')
+    if not (1 <= H <= RASTER_MAX_SIDE and 1 <= W <= RASTER_MAX_SIDE):
+        raise ValueError(f'{what}: H and W must be in 1..{RASTER_MAX_SIDE}, got {H} x {W}')
+    focal, near, tol = float(focal), float(near), float(tol)
+    if not (math.isfinite(focal) and focal > 0 and math.isfinite(near) and near > 0):
+        raise ValueError(f'{what}: focal {focal} and near {near} must be finite and > 0')
+    if not (math.isfinite(tol) and tol >= 0):
+        raise ValueError(f'{what}: tol {tol} must be finite and >= 0')
+    if cull not in RASTER_CULLS:
+        raise ValueError(f'{what}: cull must be one of {RASTER_CULLS}, got {cull!r}')
+    if mode not in TEXTURE_MODES:
+        raise ValueError(f'{what}: mode must be one of {TEXTURE_MODES}, got {mode!r}')
+    return im, d, p, (tensors[3] if masks is not None else None), V, H, W, focal, near, tol, RASTER_CULLS.index(cull), TEXTURE_MODES.index(mode)
+
+
+def _view_args(im, d, m, p, V, H, W, focal, near, tol, cull, mode):
+    none = ptr(None)
+    return (ptr(im, torch.uint8) if V else none, ptr(d) if V else none, ptr(m, torch.bool) if m is not None and V else none,
+            ptr(p) if V else none, V, H, W, focal, near, tol, cull, mode)
+
+
+def mesh_bake_points(points, normals, images, disp, poses, focal, near=1e-3, tol=0.05, cull='back', mode='blend', masks=None):
+    """Colours for N sample points of a mesh from V views: (rgb [N, 3] uint8, wsum [N] fp32, best [N] int32).  points, normals
+    [N, 3] fp32 (the normals need no unit length), images [V, H, W, 3] uint8, disp [V, H, W] fp32: the disparities of the SAME
+    mesh rasterised into poses [V, 3, 4] (mesh_rasterize), masks [V, H, W] bool or None (False = ignore the pixel), all on the
+    GPU.  A view contributes to a point iff the point projects inside the image at planar depth >= near, faces the camera
+    (cull='back': nrm . (o - p) > 0; 'none': != 0) and at all four pixels of its bilinear footprint the disparity D is that of
+    the point's own surface, |D z - 1| <= tol (warp_views' test and default) and the mask True: a footprint that straddles an
+    occlusion edge takes nothing from that view.  The colour is the bilinear value of the image, the weight cos^2 of the
+    incidence.  mode='blend': the weighted mean over the views, 'best': the colour of the view of largest weight (the lower
+    index on a tie).  wsum = the sum of the weights (0: no view sees the point, rgb is 0), best = the view of largest weight or
+    -1.  fp64 throughout: a call equals its repetition and tests/texture_numpy.py bit for bit.  ValueError for bad shapes,
+    dtypes, CPU tensors or mixed devices.  One launch.  Detached."""
+    what = 'mesh_bake_points'
+    named = (('points', points), ('normals', normals))
+    for name, t in named:
+        if not torch.is_tensor(t):
+            raise ValueError(f'{what}: {name} must be a tensor on the GPU, got {type(t).__name__}')
+        if t.dtype != _F32:
+            raise ValueError(f'{what}: {name} must be {_F32}, got {t.dtype}')
+        if t.dim() != 2 or t.shape[1] != 3:
+            raise ValueError(f'{what}: {name} must be [N, 3], got {tuple(t.shape)}')
+    pt, nr = points.detach(), normals.detach()
+    if not (pt.is_cuda and nr.is_cuda):
+        raise ValueError(f'{what}: tensors on the GPU expected (the HIP path has no CPU path)')
+    if pt.shape != nr.shape or pt.device != nr.device:
+        raise ValueError(f'{what}: points {tuple(pt.shape)} on {pt.device} and normals {tuple(nr.shape)} on {nr.device}: one shape on one device expected')
+    if not (pt.is_contiguous() and nr.is_contiguous()):
+        raise ValueError(f'{what}: every operand must be contiguous')
+    im, d, p, m, *geom = _bake_views(what, pt.device, images, disp, poses, focal, near, tol, cull, mode, masks)
+    n = int(pt.shape[0])
+    dev = pt.device
+    rgb = torch.empty((n, 3), device=dev, dtype=torch.uint8)
+    wsum = torch.empty(n, device=dev, dtype=_F32)
+    best = torch.empty(n, device=dev, dtype=_I32)
+    none = ptr(None)
+    call('mvip_texture_bake_points', ptr(pt) if n else none, ptr(nr) if n else none, n, *_view_args(im, d, m, p, *geom),
+         ptr(rgb, torch.uint8) if n else none, ptr(wsum) if n else none, ptr(best, _I32) if n else none, stream())
+    return rgb, wsum, best
+
+
+def mesh_bake_atlas(verts, faces, texels, images, disp, poses, focal, near=1e-3, tol=0.05, cull='back', mode='blend', masks=None,
+                    order='block'):
+    """The texture atlas of a mesh baked from V views: (rgb [Ht, Wt, 3] uint8, wsum [Ht, Wt] fp32, best [Ht, Wt] int32), (Ht, Wt) =
+    texture_layout(F, texels)[:2].  Faces 2k and 2k + 1 share a block of (texels + 3)^2 texels; every owned texel is the bake
+    of mesh_bake_points at a point of its face (the barycentric lattice of `texels` steps along a leg; gutter texels take the
+    nearest point of the closed face) with the face's own fp64 normal (p1 - p0) x (p2 - p0), derived from the texel index:
+    nothing is materialised.  Texels without an owner hold 0 / 0 / -1.  verts [Nv, 3] fp32, faces [F, 3] int32; the views as in
+    mesh_bake_points.  order: how texels map to lanes ('block', the default: the texels of a block are consecutive, 11 to 19 % faster than 'row',
+    texture row-major, in tools/mesh_texture_bench.py), the same output.
+    ValueError for bad shapes, dtypes, CPU tensors, mixed devices, or a face index outside [0, Nv) (one flag read back: the only
+    synchronisation).  One launch and the flag's clear.  Detached."""
+    what = 'mesh_bake_atlas'
+    v, f = _mesh_operands(what, verts, faces)
+    im, d, p, m, *geom = _bake_views(what, v.device, images, disp, poses, focal, near, tol, cull, mode, masks)
+    if order not in TEXTURE_ORDERS:
+        raise ValueError(f'{what}: order must be one of {TEXTURE_ORDERS}, got {order!r}')
+    Nv, F = int(v.shape[0]), int(f.shape[0])
+    Ht, Wt = texture_layout(F, texels)[:2]
+    dev = v.device
+    rgb = torch.empty((Ht, Wt, 3), device=dev, dtype=torch.uint8)
+    wsum = torch.empty((Ht, Wt), device=dev, dtype=_F32)
+    best = torch.empty((Ht, Wt), device=dev, dtype=_I32)
+    flag = torch.empty(1, device=dev, dtype=_I32)
+    none = ptr(None)
+    call('mvip_texture_bake_atlas', ptr(v) if Nv else none, ptr(f, _I32) if F else none, Nv, F, int(texels), TEXTURE_ORDERS.index(order),
+         *_view_args(im, d, m, p, *geom), ptr(rgb, torch.uint8) if F else none, ptr(wsum) if F else none,
+         ptr(best, _I32) if F else none, ptr(flag, _I32), stream())
+    if int(flag.cpu()):
+        raise ValueError(f'{what}: a face index lies outside [0, {Nv})')
+    return rgb, wsum, best
+
+
+def mesh_texture_resolve(face, verts, faces, atlas, texels, poses, focal, near=1e-3):
+    """rgb [V, H, W, 3] uint8 of a textured mesh for the face maps face [V, H, W] int32 that mesh_rasterize gave for the same verts
+    [Nv, 3], faces [F, 3], poses [V, 3, 4], focal and near: per covered pixel the winner's perspective-correct barycentrics are
+    recomputed as the rasteriser's colour resolve does, mapped to the face's half block of atlas [Ht, Wt, 3] uint8 (the layout of
+    mesh_bake_atlas at `texels`) and the atlas is read bilinearly.  0 where face < 0 (or not a face of the mesh).  ValueError for
+    bad shapes, dtypes, CPU tensors or mixed devices.  One launch.  Detached."""
+    import math
+    what = 'mesh_texture_resolve'
+    v, f = _mesh_operands(what, verts, faces)
+    fm = _image_batch(what, face, _I32, 'face')
+    p = _pose_batch(what, poses, 'poses')
+    Nv, F = int(v.shape[0]), int(f.shape[0])
+    Ht, Wt = texture_layout(F, texels)[:2]
+    if not torch.is_tensor(atlas) or atlas.dtype != torch.uint8 or tuple(atlas.shape) != (Ht, Wt, 3):
+        got = f'{tuple(atlas.shape)} {atlas.dtype}' if torch.is_tensor(atlas) else type(atlas).__name__
+        raise ValueError(f'{what}: atlas must be a torch.uint8 tensor [{Ht}, {Wt}, 3] on the GPU, got {got}')
+    a = atlas.detach()
+    if not all(t.is_cuda for t in (fm, p, a)):
+        raise ValueError(f'{what}: tensors on the GPU expected (the HIP path has no CPU path)')
+    if any(t.device != v.device for t in (fm, p, a)):
+        raise ValueError(f'{what}: tensors on one device expected, got {sorted({str(t.device) for t in (v, fm, p, a)})}')
+    if not all(t.is_contiguous() for t in (fm, p, a)):
+        raise ValueError(f'{what}: every operand must be contiguous')
+    V, H, W = (int(x) for x in fm.shape)
+    if p.shape[0] != V:
+        raise ValueError(f'{what}: face {tuple(fm.shape)} and poses {tuple(p.shape)}: one V expected')
+    if not (1 <= H <= RASTER_MAX_SIDE and 1 <= W <= RASTER_MAX_SIDE):
+        raise ValueError(f'{what}: H and W must be in 1..{RASTER_MAX_SIDE}, got {H} x {W}')
+    focal, near = float(focal), float(near)
+    if not (math.isfinite(focal) and focal > 0 and math.isfinite(near) and near > 0):
+        raise ValueError(f'{what}: focal {focal} and near {near} must be finite and > 0')
+    rgb = torch.empty((V, H, W, 3), device=v.device, dtype=torch.uint8)
+    none = ptr(None)
+    call('mvip_texture_resolve', ptr(fm, _I32) if V else none, ptr(v) if Nv else none, ptr(f, _I32) if F else none, Nv, F,
+         ptr(a, torch.uint8) if F else none, int(texels), ptr(p) if V else none, V, H, W, focal, near,
+         ptr(rgb, torch.uint8) if V else none, stream())
+    return rgb

@@ -5,7 +5,7 @@ binary PLY (mvip_nerf_amd/mesh.py).  Prints sigma percentiles of the grid (to ch
   python tools/extract_mesh.py CKPT.tar --out mesh.ply [--model mlp|tcnn] [--bound-min x y z --bound-max x y z]
          [--resolution 256] [--threshold 10] [--network fine|coarse] [--precision fp32|split] [--no-colors]
          [--keep-largest K] [--min-component N] [--smooth ITERS] [--simplify STEPS] [--simplify-placement quadric|mean]
-         [--drop-unseen --datadir SCENE [--factor 4]]
+         [--drop-unseen --datadir SCENE [--factor 4]] [--texture N [--texture-from render|dataset] --out mesh.obj]
   python tools/extract_mesh.py --tsdf --fixture [--iters 1500] --out mesh.ply [--trunc T] [--view-step S] ...
   python tools/extract_mesh.py --tsdf CKPT.tar --datadir SCENE [--factor 4] --out mesh.ply [--trunc T] [--view-step S] ...
 
@@ -23,6 +23,13 @@ Without the two flags the file is what it was.
 the faces that win a pixel in at least one of them, with the vertices those faces use: the interior sheets and back shells
 of a sigma level set go.  It comes last, after the clean-up.  The cameras are those of --tsdf; without --tsdf they are read
 from --datadir / --factor.  Without the flag the file is what it was.
+
+--texture N bakes a texture atlas of N texels along every face's leg (1..32) from the training views (mesh.bake_texture,
+csrc/texture.hip) and writes Wavefront OBJ + MTL + PNG; --out must end in .obj.  It comes after all clean-up and after
+--drop-unseen, so it textures the mesh that is written.  The images are renders of the field at the training cameras
+(--texture-from render, the default) or the loader's images (--texture-from dataset); the cameras are those of --tsdf, else
+--datadir / --factor.  Texels that no view sees are filled from the field (the head-on query of the vertex colours).  --out
+*.obj without --texture writes the OBJ alone, with no texture coordinates.  Without the two flags every output is what it was.
 
 --tsdf meshes what the renderer sees instead of thresholding sigma (mesh.fuse_depths): the disparity of every view (every
 S-th with --view-step S) is rendered and fused into a truncated signed distance field whose zero level set is extracted
@@ -105,6 +112,42 @@ def drop_unseen(a, m, hwf, poses):
     return out, t
 
 
+def view_images(a, te, hwf, poses, near, far, dataset):
+    """--texture: uint8 images [V, H, W, 3] of the cameras poses: renders of the field, or dataset() with --texture-from dataset."""
+    if a.texture_from == 'dataset':
+        im = torch.as_tensor(dataset()).to(poses.device)
+        return im if im.dtype == torch.uint8 else (im.float() * 255.0 + 0.5).floor().clamp(0, 255).to(torch.uint8)
+    H, W, focal = int(hwf[0]), int(hwf[1]), float(hwf[2])
+    kw = dict(te, near=near, far=far)
+    with torch.no_grad():
+        rgb = torch.stack([run.render(H, W, focal, chunk=1 << 15, c2w=poses[n], **kw)[0].reshape(H, W, 3) for n in range(poses.shape[0])])
+    return (rgb.float() * 255.0 + 0.5).floor().clamp(0, 255).to(torch.uint8)
+
+
+def dataset_images(a):
+    """--tsdf --texture-from dataset: the loader's images of the fused views."""
+    if a.fixture:
+        from tools import render_occupancy_ab as T
+        return np.load(T.FIXTURE)['images'][::a.view_step]
+    from mvip_nerf_amd.load_llff import load_llff_data
+    return load_llff_data(a.datadir, factor=a.factor)[0][::a.view_step]
+
+
+def write_mesh(a, m, te, hwf, poses, near, far, dataset):
+    """Writes a.out: PLY, or OBJ (+ MTL + PNG with --texture).  (seconds of the bake, seconds of the write)."""
+    if not a.out.endswith('.obj'):
+        return 0.0, _timed(lambda: mesh.save_ply(a.out, m))[1]
+    tex, t_tex = None, 0.0
+    if a.texture:
+        images, t_img = _timed(lambda: view_images(a, te, hwf, poses, near, far, dataset))
+        tex, t_tex = _timed(lambda: mesh.bake_texture(m, hwf, poses, images, texels=a.texture, render_kwargs=te, network=a.network))
+        print(f'texture from {poses.shape[0]} views of {int(hwf[0])} x {int(hwf[1])} ({a.texture_from}): {tuple(tex.image.shape[:2])} texels, '
+              f'images {t_img * 1e3:.1f} ms, bake {t_tex * 1e3:.1f} ms')
+    files, t_out = _timed(lambda: mesh.save_obj(a.out, m, tex))
+    print('wrote ' + ', '.join(files))
+    return t_tex, t_out
+
+
 def main_tsdf(ap, a, res, dev):
     """--tsdf: render the views' disparities, fuse them, extract the zero level set over the observed cells."""
     from mvip_nerf_amd import prepare
@@ -113,6 +156,7 @@ def main_tsdf(ap, a, res, dev):
         ap.error('--tsdf: either --fixture, or a checkpoint with --datadir; --view-step >= 1')
     if a.model != 'mlp':
         ap.error('--tsdf: the cameras are taken with the mlp model only')
+    dataset = lambda: dataset_images(a)
     (te, hwf, poses, _, _, names, near, far, source), t_model = _timed(
         lambda: P.fixture_scene(dev, a.iters) if a.fixture else P.checkpoint_scene(dev, a.ckpt, a.datadir, a.factor))
     for net in (te['network_fn'], te.get('network_fine')):
@@ -142,11 +186,12 @@ def main_tsdf(ap, a, res, dev):
     colors, t_col = (None, 0.0) if a.no_colors else _timed(lambda: mesh.vertex_colors(te, verts, normals, a.network))
     m, t_clean = clean_up(a, mesh.Mesh(verts, faces, normals, colors), lo32, hi32, res)
     m, t_seen = drop_unseen(a, m, hwf, poses)
-    _, t_ply = _timed(lambda: mesh.save_ply(a.out, m))
+    t_tex, t_ply = write_mesh(a, m, te, hwf, poses, near, far, dataset)
     print(f'tsdf zero level set: {m.verts.shape[0]} vertices, {m.faces.shape[0]} triangles -> {a.out}')
     print(f'time  model {t_model * 1e3:.1f} ms  render {t_render * 1e3:.1f} ms  fusion {t_fuse * 1e3:.1f} ms  components {t_cc * 1e3:.1f} ms  '
           f'marching cubes {t_mc * 1e3:.1f} ms  colours {t_col * 1e3:.1f} ms  clean-up {t_clean * 1e3:.1f} ms  '
-          + (f'visibility {t_seen * 1e3:.1f} ms  ' if a.drop_unseen else '') + f'write {t_ply * 1e3:.1f} ms')
+          + (f'visibility {t_seen * 1e3:.1f} ms  ' if a.drop_unseen else '') + (f'texture {t_tex * 1e3:.1f} ms  ' if a.texture else '')
+          + f'write {t_ply * 1e3:.1f} ms')
     return 0
 
 
@@ -170,6 +215,10 @@ def main(argv=None):
     ap.add_argument('--simplify-placement', choices=('quadric', 'mean'), default='quadric')
     ap.add_argument('--drop-unseen', action='store_true',
                     help='write only the faces some training view sees (cameras: those of --tsdf, else --datadir / --factor)')
+    ap.add_argument('--texture', type=int, default=0, metavar='N',
+                    help='bake a texture atlas of N texels per face leg from the training views and write OBJ + MTL + PNG (0: off)')
+    ap.add_argument('--texture-from', choices=('render', 'dataset'), default='render',
+                    help='--texture: the images are renders of the field at the training cameras, or the dataset\'s')
     ap.add_argument('--tsdf', action='store_true', help='fuse rendered depth maps instead of thresholding sigma')
     ap.add_argument('--fixture', action='store_true', help='--tsdf: train the scene-1 fixture and use its cameras')
     ap.add_argument('--iters', type=int, default=1500, help='training iterations of --fixture')
@@ -180,12 +229,14 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if a.smooth < 0 or not a.simplify >= 0:
         ap.error('--smooth and --simplify must be >= 0')
+    if not 0 <= a.texture <= 32 or (a.texture and not a.out.endswith('.obj')):
+        ap.error('--texture: 1..32 texels, and --out must end in .obj')
     res = a.resolution[0] if len(a.resolution) == 1 else tuple(a.resolution)
     dev = torch.device('cuda', 0)
     if a.tsdf:
         return main_tsdf(ap, a, res, dev)
-    if a.fixture or a.ckpt is None or bool(a.datadir) != a.drop_unseen:
-        ap.error('a checkpoint is required; --fixture belongs to --tsdf, --datadir to --tsdf or --drop-unseen (which needs it)')
+    if a.fixture or a.ckpt is None or bool(a.datadir) != (a.drop_unseen or bool(a.texture)):
+        ap.error('a checkpoint is required; --fixture belongs to --tsdf, --datadir to --tsdf, --drop-unseen or --texture (which need it)')
     a.bound_min = (-1.0, -1.0, -1.0) if a.bound_min is None else a.bound_min
     a.bound_max = (1.0, 1.0, 1.0) if a.bound_max is None else a.bound_max
     kw, step = load_model(a.ckpt, a.model, dev)
@@ -214,15 +265,20 @@ def main(argv=None):
     (verts, faces, normals), t_mc = timed(lambda: mesh.marching_cubes(grid, a.threshold, a.bound_min, a.bound_max))
     colors, t_col = (None, 0.0) if a.no_colors else timed(lambda: mesh.vertex_colors(kw, verts, normals, a.network))
     m, t_clean = clean_up(a, mesh.Mesh(verts, faces, normals, colors), a.bound_min, a.bound_max, res)
-    t_seen = 0.0
-    if a.drop_unseen:
+    t_seen, hwf, cam_poses, near, far, loaded = 0.0, None, None, None, None, None
+    if a.drop_unseen or a.texture:
         from mvip_nerf_amd.load_llff import load_llff_data
-        cams = load_llff_data(a.datadir, factor=a.factor)[1]
-        m, t_seen = drop_unseen(a, m, tuple(float(v) for v in cams[0, :3, -1]), torch.from_numpy(cams[:, :3, :4].copy()).to(dev))
-    _, t_ply = timed(lambda: mesh.save_ply(a.out, m))
+        loaded = load_llff_data(a.datadir, factor=a.factor)
+        cams, bds = loaded[1], loaded[2]
+        hwf, cam_poses = tuple(float(v) for v in cams[0, :3, -1]), torch.from_numpy(cams[:, :3, :4].copy()).to(dev)
+        near, far = float(bds.min() * .9), float(bds.max() * 1.)
+    if a.drop_unseen:
+        m, t_seen = drop_unseen(a, m, hwf, cam_poses)
+    t_tex, t_ply = write_mesh(a, m, kw, hwf, cam_poses, near, far, lambda: loaded[0])
     print(f'threshold {a.threshold}: {m.verts.shape[0]} vertices, {m.faces.shape[0]} triangles -> {a.out}')
     print(f'time  density grid {t_grid * 1e3:.1f} ms  components {t_cc * 1e3:.1f} ms  marching cubes {t_mc * 1e3:.1f} ms  colours {t_col * 1e3:.1f} ms  '
-          f'clean-up {t_clean * 1e3:.1f} ms  ' + (f'visibility {t_seen * 1e3:.1f} ms  ' if a.drop_unseen else '') + f'write {t_ply * 1e3:.1f} ms')
+          f'clean-up {t_clean * 1e3:.1f} ms  ' + (f'visibility {t_seen * 1e3:.1f} ms  ' if a.drop_unseen else '')
+          + (f'texture {t_tex * 1e3:.1f} ms  ' if a.texture else '') + f'write {t_ply * 1e3:.1f} ms')
     return 0
 
 
