@@ -1093,6 +1093,44 @@ int mvip_texture_resolve(const int *face, const float *verts, const int *faces, 
                          const void *atlas, int texels, const float *poses, int64_t n_views, int H, int W, double focal,
                          double znear, void *rgb, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mesh-to-mesh distance: the closest point of a triangle mesh to each of N query points on a uniform grid of face lists, and
+ * deterministic surface samples (beyond the reference, which has no mesh export: no entry point has a reference call site;
+ * csrc/mesh_distance.hip, ops.mesh_face_grid / mesh_closest_point / mesh_sample_faces, evaluate.mesh_distance_metrics).  The
+ * definition, in fp64 with its operation order, is written out in csrc/mesh_distance.hip and tests/mesh_distance_numpy.py;
+ * the result does not depend on the grid.  All operands DEVICE memory, dense, except box / cells (host): verts [V,3] fp32,
+ * faces [F,3] int32; box = (bmin[3], inv[3]) and cells[3] (each 1..512) of the bit grid above.  MVIP_EINVAL (-1 from the size
+ * query) before any device call for: a count < 0, V, 3 F, N or a pair / sample count > 2^31 - 1, F = 0 (V = 0), a bad box /
+ * cells, k outside 1..1024, a NULL operand that a non-zero count makes necessary.  N = 0 is valid.  Every launch goes on the
+ * caller's stream; integer atomics only: the outputs are bit-reproducible.
+ * mvip_mesh_distance_grid_count: clears flag[0]; face_offsets [F] 64-bit = the exclusive scan, in face order, of the number of
+ *   cells each face's bounding box overlaps (cell range of its fp32 minimum and maximum by the bit grid's rule, clamped to the
+ *   grid); total[0] = the number of (cell, face) pairs; flag[0] bit 0: a face index outside [0, V), bit 1: a NaN or infinite
+ *   vertex of a face (such a face counts 0 pairs).  total and flag are the caller's one read; a total above 2^31 - 1 is the
+ *   caller's error (mvip_mesh_distance_grid_scratch_words and mvip_mesh_distance_grid_fill answer it with -1 / MVIP_EINVAL).
+ * mvip_mesh_distance_grid_scratch_words: int32 words of `scratch` of mvip_mesh_distance_grid_fill (8-byte aligned).
+ * mvip_mesh_distance_grid_fill: from face_offsets and n_pairs = total[0] of the count for the same mesh and grid:
+ *   cell_offsets [n_cells + 1], cell_faces [n_pairs]; cell_faces[cell_offsets[l] : cell_offsets[l+1]] = the faces entered in
+ *   linear cell l, ascending.  The lists are those of mvip_mesh_corner_table over the pairs' cell keys.
+ * mvip_mesh_distance_query: face [N] (-1 for a query with a NaN or infinite coordinate), point [N,3], dist [N] (NaN there).
+ *   stats: NULL, or two 64-bit words that are cleared and receive the number of point-face tests and, summed over the waves,
+ *   64 times the tests of the wave's busiest lane (a counting variant; their ratio is the lane utilisation of the face loop).
+ * mvip_mesh_sample_faces: the k^2 centroids of the uniform subdivision of every face, face-major: points [F k^2, 3] fp32,
+ *   face_of_sample [F k^2] int32, weights [F k^2] fp64 (area(f) / k^2).  Clears flag[0]; bit 0: a face index outside [0, V)
+ *   (its samples are 0 with weight 0). */
+int mvip_mesh_distance_grid_count(const float *verts, const int *faces, int64_t n_verts, int64_t n_faces, const float *box,
+                                  const int *cells, int64_t *face_offsets, int64_t *total, int *flag, void *stream);
+int64_t mvip_mesh_distance_grid_scratch_words(int64_t n_pairs, const int *cells);
+int mvip_mesh_distance_grid_fill(const float *verts, const int *faces, int64_t n_verts, int64_t n_faces, const float *box,
+                                 const int *cells, const int64_t *face_offsets, int64_t n_pairs, int *cell_offsets,
+                                 int *cell_faces, int *scratch, void *stream);
+int mvip_mesh_distance_query(const float *points, int64_t n_points, const float *verts, const int *faces, int64_t n_verts,
+                             int64_t n_faces, const float *box, const int *cells, const int *cell_offsets,
+                             const int *cell_faces, int64_t n_pairs, int *face, float *point, float *dist, void *stats,
+                             void *stream);
+int mvip_mesh_sample_faces(const float *verts, const int *faces, int64_t n_verts, int64_t n_faces, int k, float *points,
+                           int *face_of_sample, double *weights, int *flag, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -227,6 +227,14 @@ _SIGNATURES = {
                                        ctypes.c_double, ctypes.c_double, _int, _int, _c_f, _c_f, _c_f, _c_f, _c_f]),
     'mvip_texture_resolve': (_int, [_c_f, _c_f, _c_f, _i64, _i64, _c_f, _int, _c_f, _i64, _int, _int, ctypes.c_double, ctypes.c_double,
                                     _c_f, _c_f]),
+    'mvip_mesh_distance_grid_count': (_int, [_c_f, _c_f, _i64, _i64, ctypes.POINTER(_flt), ctypes.POINTER(_int), _c_f, _c_f, _c_f,
+                                             _c_f]),
+    'mvip_mesh_distance_grid_scratch_words': (_i64, [_i64, ctypes.POINTER(_int)]),
+    'mvip_mesh_distance_grid_fill': (_int, [_c_f, _c_f, _i64, _i64, ctypes.POINTER(_flt), ctypes.POINTER(_int), _c_f, _i64, _c_f,
+                                            _c_f, _c_f, _c_f]),
+    'mvip_mesh_distance_query': (_int, [_c_f, _i64, _c_f, _c_f, _i64, _i64, ctypes.POINTER(_flt), ctypes.POINTER(_int), _c_f, _c_f,
+                                        _i64, _c_f, _c_f, _c_f, _c_f, _c_f]),
+    'mvip_mesh_sample_faces': (_int, [_c_f, _c_f, _i64, _i64, _int, _c_f, _c_f, _c_f, _c_f, _c_f]),
 }
 
 # every symbol include/mvip_nerf.h declares; tests check the built library exports all of them

@@ -251,6 +251,77 @@ def mesh_image_metrics(mesh, texture, hwf, poses, images, masks=None, near=1e-3,
     return summarise(per_view)
 
 
+def _unit_face_normals(verts, faces):
+    """(unit normals [F, 3] fp64, zero for a degenerate face; degenerate [F] bool) on the host: N = (b - a) x (c - a) of the
+    widened fp32 vertices, N / sqrt(N . N); degenerate iff not N . N > 0."""
+    v = verts.detach().cpu().numpy().astype(np.float64)
+    f = faces.detach().cpu().numpy().astype(np.int64)
+    with np.errstate(divide='ignore', invalid='ignore'):                              # a NaN vertex: its faces count as degenerate
+        u, w = v[f[:, 1]] - v[f[:, 0]], v[f[:, 2]] - v[f[:, 0]]
+        N = np.stack([u[:, 1] * w[:, 2] - u[:, 2] * w[:, 1], u[:, 2] * w[:, 0] - u[:, 0] * w[:, 2], u[:, 0] * w[:, 1] - u[:, 1] * w[:, 0]], -1)
+        nn = (N[:, 0] * N[:, 0] + N[:, 1] * N[:, 1]) + N[:, 2] * N[:, 2]
+        bad = ~(nn > 0.0)
+        return np.where(bad[:, None], 0.0, N / np.sqrt(nn)[:, None]), bad
+
+
+def mesh_distance_direction(dist, weights, normals_from, face_of_sample, normals_to, hit_face, thresholds):
+    """One direction of mesh_distance_metrics from the samples' distances (host arrays): dist [n] fp32, weights [n] fp64,
+    normals_* = _unit_face_normals(...) of the sampled and of the queried mesh, face_of_sample / hit_face [n].  Every sum is
+    numpy's sum of the elementwise products in sample order, in fp64 -- a fixed order, so the report is bit-reproducible:
+    W = sum(w); mean = sum(w d) / W; rms = sqrt(sum(w d d) / W); max = max(d); within[tau] = sum(w where d <= tau) / W;
+    normal_consistency = sum(w |n . n'|) / sum(w) over the samples whose own face and hit face both are non-degenerate."""
+    d = np.asarray(dist, np.float32).astype(np.float64)
+    w = np.asarray(weights, np.float64)
+    W = np.sum(w)
+    (nf, bad_f), (nt, bad_t) = normals_from, normals_to
+    fos, hit = np.asarray(face_of_sample, np.int64), np.asarray(hit_face, np.int64)
+    a, b = nf[fos], nt[hit]
+    c = np.abs((a[:, 0] * b[:, 0] + a[:, 1] * b[:, 1]) + a[:, 2] * b[:, 2])
+    wk = np.where(~bad_f[fos] & ~bad_t[hit], w, 0.0)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return {'samples': int(len(d)), 'area': float(W), 'mean': float(np.sum(w * d) / W), 'rms': float(np.sqrt(np.sum(w * d * d) / W)),
+                'max': float(np.max(d)), 'within': [float(np.sum(np.where(d <= np.float64(t), w, 0.0)) / W) for t in thresholds],
+                'normal_consistency': float(np.sum(wk * c) / np.sum(wk))}
+
+
+def mesh_distance_metrics(mesh_a, mesh_b, samples=2, thresholds=()):
+    """How far two triangle meshes lie from each other, over their whole surfaces (beyond the reference, which has no mesh
+    export).  mesh_a / mesh_b: mesh.Mesh, or (verts [V, 3] fp32, faces [F, 3] int32) on the GPU.  Each mesh is sampled with
+    ops.mesh_sample_faces at subdivision `samples` (samples^2 equal-area points per face, nothing random) and every sample's
+    closest point on the other mesh found with ops.mesh_closest_point (csrc/mesh_distance.hip).  The report, a dict:
+      a_to_b, b_to_a: {samples, area, mean, rms, max, within [per threshold], normal_consistency} -- area-weighted over the
+        samples of the first mesh (mesh_distance_direction);
+      chamfer = the mean of the two means; hausdorff = the larger of the two maxima (a sampled Hausdorff distance);
+      thresholds; precision = a_to_b's within, recall = b_to_a's, fscore = 2 P R / (P + R) (0 where P + R == 0), per threshold;
+      normal_consistency = the mean of the two directions' area-weighted means of |n_a . n_b| (unit fp64 face normals of the
+        sample's own face and of the face it hits; degenerate faces excluded on both sides).
+    The kernels are deterministic and the reductions run on the host in a fixed order: two calls give the same bits.
+    ValueError for samples < 1, a mesh without faces, thresholds that are not finite and >= 0."""
+    from . import ops
+    import math
+    ts = [float(t) for t in thresholds]
+    if not all(math.isfinite(t) and t >= 0 for t in ts):
+        raise ValueError(f'mesh_distance_metrics: thresholds must be finite and >= 0, got {list(thresholds)!r}')
+    pairs = [(m.verts, m.faces) if hasattr(m, 'verts') else (m[0], m[1]) for m in (mesh_a, mesh_b)]
+    for v, f in pairs:
+        if not torch.is_tensor(f) or f.dim() != 2 or f.shape[0] == 0:
+            raise ValueError('mesh_distance_metrics: both meshes need at least one face')
+    normals = [_unit_face_normals(v, f) for v, f in pairs]
+    grids = [ops.mesh_face_grid(v.detach().contiguous(), f.detach().contiguous()) for v, f in pairs]
+    out = []
+    for src, dst in ((0, 1), (1, 0)):
+        pts, fos, w = ops.mesh_sample_faces(pairs[src][0], pairs[src][1], samples)
+        g = grids[dst]
+        face, _, dist = ops.mesh_closest_point(pts, g.verts, g.faces, grid=g)
+        out.append(mesh_distance_direction(dist.cpu().numpy(), w.cpu().numpy(), normals[src], fos.cpu().numpy(), normals[dst],
+                                           face.cpu().numpy(), ts))
+    ab, ba = out
+    P, R = ab['within'], ba['within']
+    return {'thresholds': ts, 'a_to_b': ab, 'b_to_a': ba, 'chamfer': (ab['mean'] + ba['mean']) / 2.0, 'hausdorff': max(ab['max'], ba['max']),
+            'precision': list(P), 'recall': list(R), 'fscore': [2.0 * p * r / (p + r) if p + r > 0 else 0.0 for p, r in zip(P, R)],
+            'normal_consistency': (ab['normal_consistency'] + ba['normal_consistency']) / 2.0}
+
+
 def evaluate_folders(pred_dir, gt_dir, mask_dir=None, device=None):
     """The metrics of the images of pred_dir against those of gt_dir (8-bit, read with load_llff._imread, / 255), paired by
     sorted name (pair_names: a name without a partner is an error); mask_dir: one mask per pair (non-zero = masked).  Returns

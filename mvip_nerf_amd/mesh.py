@@ -13,6 +13,8 @@ face-id and colour maps it presents to each view, the faces any view sees, and t
 bake_texture() / colors_from_views() / render_textured() / save_obj() take the colour from the views instead of the field
 (csrc/texture.hip): a per-face texture atlas or vertex colours blended from the images of the cameras that see each point,
 the textured mesh rendered back into a camera, and OBJ + MTL + PNG export.
+load_ply() reads back what save_ply() wrote, bit for bit; how far two meshes lie apart is evaluate.mesh_distance_metrics
+(csrc/mesh_distance.hip).
 
 Conventions (shared with csrc/mcubes.hip and the test restatement tests/mc_numpy.py): grid [nx, ny, nz], z fastest; point
 (i, j, k) sits at bmin + (i, j, k) * (bmax - bmin) / (n - 1), in fp32 arithmetic; a corner is inside iff sigma >= threshold
@@ -746,6 +748,49 @@ def save_ply(path, mesh):
         fh.write(('\n'.join(head) + '\n').encode('ascii'))
         fh.write(vert.tobytes())
         fh.write(face.tobytes())
+
+
+def load_ply(path, device=None):
+    """Mesh(verts, faces, normals, colors) of a PLY file that save_ply wrote -- that layout only: binary little-endian, float x y z
+    nx ny nz, optionally uchar red green blue, triangles as `uchar int` lists.  The round trip is bit-exact.  device=None: numpy
+    arrays (fp32 [V, 3], int32 [F, 3], fp32 [V, 3], uint8 [V, 3] or None); otherwise tensors on `device`.  ValueError for any
+    other header, a face that is not a triangle, or a file of the wrong length."""
+    with open(path, 'rb') as fh:
+        blob = fh.read()
+    end = blob.find(b'end_header\n')
+    if end < 0:
+        raise ValueError(f'load_ply: {path}: no PLY header')
+    head = blob[:end].decode('ascii', 'replace').split('\n')
+    body = blob[end + len(b'end_header\n'):]
+    lines = [ln for ln in head if ln and not ln.startswith('comment')]
+    props = [f'property float {k}' for k in ('x', 'y', 'z', 'nx', 'ny', 'nz')]
+    rgb = ['property uchar red', 'property uchar green', 'property uchar blue']
+    try:
+        if lines[:2] != ['ply', 'format binary_little_endian 1.0'] or not lines[2].startswith('element vertex '):
+            raise ValueError
+        V = int(lines[2].split()[2])
+        colored = lines[3 + len(props):3 + len(props) + 3] == rgb
+        rest = lines[3 + len(props) + (3 if colored else 0):]
+        if lines[3:3 + len(props)] != props or len(rest) != 2 or not rest[0].startswith('element face ') \
+                or rest[1] != 'property list uchar int vertex_indices':
+            raise ValueError
+        F = int(rest[0].split()[2])
+    except (ValueError, IndexError):
+        raise ValueError(f'load_ply: {path}: not the header save_ply writes') from None
+    vfields = [(k, '<f4') for k in ('x', 'y', 'z', 'nx', 'ny', 'nz')] + ([(k, 'u1') for k in ('red', 'green', 'blue')] if colored else [])
+    vdt, fdt = np.dtype(vfields), np.dtype([('n', 'u1'), ('v', '<i4', (3,))])
+    if V < 0 or F < 0 or len(body) != V * vdt.itemsize + F * fdt.itemsize:
+        raise ValueError(f'load_ply: {path}: {len(body)} bytes for {V} vertices and {F} triangles')
+    vert = np.frombuffer(body, vdt, V)
+    face = np.frombuffer(body, fdt, F, offset=V * vdt.itemsize)
+    if F and not np.all(face['n'] == 3):
+        raise ValueError(f'load_ply: {path}: a face that is not a triangle')
+    out = [np.stack([vert['x'], vert['y'], vert['z']], -1).astype(np.float32), np.ascontiguousarray(face['v'], np.int32).reshape(F, 3),
+           np.stack([vert['nx'], vert['ny'], vert['nz']], -1).astype(np.float32),
+           np.stack([vert['red'], vert['green'], vert['blue']], -1).astype(np.uint8) if colored else None]
+    if device is not None:
+        out = [None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(device) for a in out]
+    return Mesh(*out)
 
 
 def _host(a, dtype):

@@ -2705,6 +2705,193 @@ def mesh_cluster(verts, faces, colors, origin, cell, placement='quadric', dedupe
     return out_v, out_f, out_c, cov
 
 
+# mesh-to-mesh distance: closest-point queries on a grid of face lists, surface samples (beyond the reference, csrc/mesh_distance.hip)
+# The definition is csrc/mesh_distance.hip's and tests/mesh_distance_numpy.py's.  There is no CPU path.
+
+FACE_GRID_MAX_CELLS_PER_AXIS = 512
+# a cell is never narrower than this share of the largest coordinate magnitude (the margin argument of csrc/mesh_distance.hip)
+FACE_GRID_MIN_CELL_SHARE = 2.0 ** -20
+MESH_SAMPLE_MAX_SUBDIVISION = 1024
+
+
+class FaceGrid:
+    """The face lists of one mesh on a uniform grid (ops.mesh_face_grid): reusable for any number of mesh_closest_point calls
+    on the same verts / faces tensors.  box = (bmin[3], inv[3]) fp32, cells (cx, cy, cz), cell_offsets [n_cells + 1] int32,
+    cell_faces [n_pairs] int32 (each cell's faces ascending), n_pairs."""
+
+    def __init__(self, verts, faces, box, cells, cell_offsets, cell_faces):
+        self.verts, self.faces, self.box, self.cells = verts, faces, box, cells
+        self.cell_offsets, self.cell_faces = cell_offsets, cell_faces
+        self.n_pairs = int(cell_faces.shape[0])
+        self._key = self._key_of(verts, faces)
+
+    @staticmethod
+    def _key_of(v, f):
+        return (v.data_ptr(), tuple(v.shape), v._version, f.data_ptr(), tuple(f.shape), f._version, str(v.device))
+
+    def matches(self, verts, faces):
+        return self._key == self._key_of(verts, faces)
+
+
+def mesh_face_grid_cells(lo, hi, n_faces, cells=None):
+    """(box fp32 [6] = (bmin, inv), cells (cx, cy, cz)) of the face grid over the bounding box lo .. hi (fp32 [3]) of a mesh of
+    n_faces faces.  Host code.  Default: cubic cells of edge h = (the product of the non-zero extents / n_faces)^(1 / their number),
+    about one cell per face; ceil(extent / h) cells per axis clamped to 1..512, inv = fp32(1 / h) on all axes.  cells (an int or
+    three): that many per axis, inv = fp32(cells / extent) per axis.  An axis of zero extent has one cell and inv 1.  Every count
+    is then cut down so that no cell is narrower than 2^-20 of the largest coordinate magnitude (never on a sane mesh).
+    ValueError for non-finite bounds or counts outside 1..512."""
+    import math
+    import numpy as np
+    what = 'mesh_face_grid'
+    lo, hi = np.asarray(lo, np.float32).reshape(3), np.asarray(hi, np.float32).reshape(3)
+    if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi))):
+        raise ValueError(f'{what}: a vertex is NaN or infinite')
+    ext = hi.astype(np.float64) - lo.astype(np.float64)
+    if not np.all(np.isfinite(ext.astype(np.float32))) or np.any(ext < 0):
+        raise ValueError(f'{what}: the bounding box {lo.tolist()} .. {hi.tolist()} has no finite fp32 extent')
+    scale = float(max(np.abs(lo).max(), np.abs(hi).max()))
+    narrowest = scale * FACE_GRID_MIN_CELL_SHARE
+    cap = [FACE_GRID_MAX_CELLS_PER_AXIS if narrowest == 0 else int(max(1, min(FACE_GRID_MAX_CELLS_PER_AXIS, math.floor(e / narrowest))))
+           for e in ext]
+    if cells is None:
+        nz = [e for e in ext if e > 0]
+        if not nz:
+            counts, h = [1, 1, 1], 1.0
+        else:
+            h = (float(np.prod(nz)) / max(int(n_faces), 1)) ** (1.0 / len(nz))
+            counts = [1 if e == 0 else int(max(1, min(cap[a], math.ceil(e / h * (1.0 - 1e-12))))) for a, e in enumerate(ext)]
+            h = max(h, max(e / c for e, c in zip(ext, counts)))                  # clamped counts: the cells grow, still cubic
+        inv = [np.float32(1.0) if e == 0 else np.float32(1.0 / h) for e in ext]
+    else:
+        counts = [int(cells)] * 3 if np.isscalar(cells) else [int(c) for c in cells]
+        if len(counts) != 3 or not all(1 <= c <= FACE_GRID_MAX_CELLS_PER_AXIS for c in counts):
+            raise ValueError(f'{what}: cells must be one or three counts in 1..{FACE_GRID_MAX_CELLS_PER_AXIS}, got {cells!r}')
+        counts = [1 if e == 0 else min(c, cap[a]) for a, (e, c) in enumerate(zip(ext, counts))]
+        inv = [np.float32(1.0) if e == 0 else np.float32(c / e) for e, c in zip(ext, counts)]
+    if not all(math.isfinite(float(i)) and i > 0 for i in inv):
+        raise ValueError(f'{what}: 1 / cell is not a finite fp32 number > 0 for the box {lo.tolist()} .. {hi.tolist()}')
+    return np.concatenate([lo, np.asarray(inv, np.float32)]).astype(np.float32), tuple(counts)
+
+
+def mesh_face_grid(verts, faces, cells=None):
+    """The reusable FaceGrid of an indexed mesh for mesh_closest_point (the definition: csrc/mesh_distance.hip): a uniform grid
+    over the mesh's bounding box (mesh_face_grid_cells: about one cubic cell per face by default, `cells` = an int or three counts
+    for the tests) with every face entered in every cell its bounding box overlaps, each cell's list ascending in the face index.
+    Built from per-face counts, an exclusive scan, the (cell, face) pairs in face order and the lists of mesh_corner_table over
+    the cell keys.  ValueError for F = 0, a face index outside [0, V), a NaN or infinite vertex, more than 2^31 - 1 pairs.  Reads
+    back the vertex bounds, then the pair total with the flag."""
+    import ctypes
+    import numpy as np
+    what = 'mesh_face_grid'
+    v, f = _mesh_operands(what, verts, faces)
+    V, F = int(v.shape[0]), int(f.shape[0])
+    if F == 0 or V == 0:
+        raise ValueError(f'{what}: a mesh of {F} faces and {V} vertices has no closest point')
+    dev = v.device
+    lohi = torch.stack([v.amin(0), v.amax(0)]).cpu().numpy()
+    box, counts = mesh_face_grid_cells(lohi[0], lohi[1], F, cells)
+    cbox = (ctypes.c_float * 6)(*[float(x) for x in box])
+    ccells = (ctypes.c_int * 3)(*counts)
+    st = stream()
+    face_off = torch.empty(F, device=dev, dtype=torch.int64)
+    meta = torch.empty(2, device=dev, dtype=torch.int64)                     # [0] the pair total, [1] (low word) the flag
+    call('mvip_mesh_distance_grid_count', ptr(v), ptr(f, _I32), V, F, cbox, ccells, ptr(face_off, torch.int64), ptr(meta, torch.int64),
+         ctypes.c_void_p(meta.data_ptr() + 8), st)
+    host = meta.cpu().numpy()
+    P, flag = int(host[0]), int(host.view(np.int32)[2])
+    if flag & 1:
+        raise ValueError(f'{what}: a face index lies outside [0, {V})')
+    if flag & 2:
+        raise ValueError(f'{what}: a vertex is NaN or infinite')
+    words = _lib.load().mvip_mesh_distance_grid_scratch_words(P, ccells)
+    if P > 2 ** 31 - 1 or words < 0:
+        raise ValueError(f'{what}: {P} (cell, face) pairs on {counts} cells exceed int32 indices: use fewer cells')
+    K = counts[0] * counts[1] * counts[2]
+    cell_off = torch.empty(K + 1, device=dev, dtype=_I32)
+    cell_faces = torch.empty(P, device=dev, dtype=_I32)
+    scratch = torch.empty(words, device=dev, dtype=_I32)
+    call('mvip_mesh_distance_grid_fill', ptr(v), ptr(f, _I32), V, F, cbox, ccells, ptr(face_off, torch.int64), P, ptr(cell_off, _I32),
+         ptr(cell_faces, _I32), ptr(scratch, _I32), st)
+    return FaceGrid(v, f, box, counts, cell_off, cell_faces)
+
+
+def mesh_closest_point(points, verts, faces, grid=None, return_stats=False):
+    """The closest point of the mesh (verts [V, 3] fp32, faces [F, 3] int32) to each of points [N, 3] fp32, all on the GPU:
+    (face [N] int32, point [N, 3] fp32, dist [N] fp32).  The definition (csrc/mesh_distance.hip, tests/mesh_distance_numpy.py):
+    per face the exact point-triangle distance in fp64 on the widened inputs, a degenerate face being its edges; the face of
+    smallest squared distance, the lowest index among equals; point and dist rounded to fp32 once.  A query with a NaN or
+    infinite coordinate gives face -1 and NaN.  grid: a FaceGrid of mesh_face_grid for these very tensors (None: built here);
+    the result does not depend on it.  return_stats=True appends a [2] int64 device tensor (a counting variant of the kernel):
+    the number of point-face tests and, summed over the waves, 64 times the tests of the wave's busiest lane.  N = 0 gives empty tensors.  ValueError for bad shapes or dtypes, CPU tensors, F = 0, a
+    face index outside [0, V), a NaN or infinite vertex, a grid of another mesh.  Detached."""
+    import ctypes
+    what = 'mesh_closest_point'
+    v, f = _mesh_operands(what, verts, faces)
+    if not torch.is_tensor(points):
+        raise ValueError(f'{what}: points must be a tensor on the GPU, got {type(points).__name__}')
+    if points.dtype != _F32:
+        raise ValueError(f'{what}: points must be {_F32}, got {points.dtype}')
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f'{what}: points must be [N, 3], got {tuple(points.shape)}')
+    p = points.detach()
+    if not p.is_cuda:
+        raise ValueError(f'{what}: tensors on the GPU expected (the HIP path has no CPU path)')
+    if p.device != v.device:
+        raise ValueError(f'{what}: tensors on one device expected, got {sorted({str(v.device), str(p.device)})}')
+    if not p.is_contiguous():
+        raise ValueError(f'{what}: every operand must be contiguous')
+    N = int(p.shape[0])
+    if 3 * N > 2 ** 31 - 1:
+        raise ValueError(f'{what}: {N} points exceed int32 indices')
+    if grid is None:
+        grid = mesh_face_grid(v, f)
+    elif not isinstance(grid, FaceGrid) or not grid.matches(v, f):
+        raise ValueError(f'{what}: grid must be the mesh_face_grid of these verts and faces')
+    V, F = int(v.shape[0]), int(f.shape[0])
+    dev = v.device
+    face = torch.empty(N, device=dev, dtype=_I32)
+    point = torch.empty((N, 3), device=dev, dtype=_F32)
+    dist = torch.empty(N, device=dev, dtype=_F32)
+    stats = torch.empty(2, device=dev, dtype=torch.int64) if return_stats else None
+    none = ptr(None)
+    cbox = (ctypes.c_float * 6)(*[float(x) for x in grid.box])
+    ccells = (ctypes.c_int * 3)(*grid.cells)
+    call('mvip_mesh_distance_query', ptr(p) if N else none, N, ptr(v), ptr(f, _I32), V, F, cbox, ccells, ptr(grid.cell_offsets, _I32),
+         ptr(grid.cell_faces, _I32) if grid.n_pairs else none, grid.n_pairs, ptr(face, _I32) if N else none, ptr(point) if N else none,
+         ptr(dist) if N else none, ptr(stats, torch.int64) if return_stats else none, stream())
+    return (face, point, dist, stats) if return_stats else (face, point, dist)
+
+
+def mesh_sample_faces(verts, faces, k):
+    """Deterministic surface samples: (points [F k^2, 3] fp32, face_of_sample [F k^2] int32, weights [F k^2] fp64), face-major.
+    The k^2 centroids of the uniform subdivision of each face into k^2 congruent triangles (upward ones first, then downward;
+    csrc/mesh_distance.hip), each carrying area(face) / k^2: an exact equal-area quadrature rule, nothing random.  fp64
+    arithmetic, points rounded to fp32.  F = 0 gives empty tensors.  ValueError for k outside 1..1024, more than 2^31 - 1
+    coordinates, a face index outside [0, V)."""
+    what = 'mesh_sample_faces'
+    v, f = _mesh_operands(what, verts, faces)
+    if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= MESH_SAMPLE_MAX_SUBDIVISION:
+        raise ValueError(f'{what}: k must be an integer in 1..{MESH_SAMPLE_MAX_SUBDIVISION}, got {k!r}')
+    k = int(k)
+    V, F = int(v.shape[0]), int(f.shape[0])
+    n = F * k * k
+    if 3 * n > 2 ** 31 - 1:
+        raise ValueError(f'{what}: {n} samples exceed int32 indices')
+    if F and V == 0:
+        raise ValueError(f'{what}: a face index lies outside [0, 0)')
+    dev = v.device
+    pts = torch.empty((n, 3), device=dev, dtype=_F32)
+    fos = torch.empty(n, device=dev, dtype=_I32)
+    w = torch.empty(n, device=dev, dtype=torch.float64)
+    flag = torch.empty(1, device=dev, dtype=_I32)
+    none = ptr(None)
+    call('mvip_mesh_sample_faces', ptr(v) if V else none, ptr(f, _I32) if F else none, V, F, k, ptr(pts) if n else none,
+         ptr(fos, _I32) if n else none, ptr(w, torch.float64) if n else none, ptr(flag, _I32), stream())
+    if int(flag.cpu()):
+        raise ValueError(f'{what}: a face index lies outside [0, {V})')
+    return pts, fos, w
+
+
 # mesh rasterisation: disparity, face ids and colours per view (beyond the reference, csrc/raster.hip) -------------------------------
 # The definition is csrc/raster.hip's and tests/raster_numpy.py's.  There is no CPU path.
 

@@ -6,6 +6,7 @@ binary PLY (mvip_nerf_amd/mesh.py).  Prints sigma percentiles of the grid (to ch
          [--resolution 256] [--threshold 10] [--network fine|coarse] [--precision fp32|split] [--no-colors]
          [--keep-largest K] [--min-component N] [--smooth ITERS] [--simplify STEPS] [--simplify-placement quadric|mean]
          [--drop-unseen --datadir SCENE [--factor 4]] [--texture N [--texture-from render|dataset] --out mesh.obj]
+         [--report-error]
   python tools/extract_mesh.py --tsdf --fixture [--iters 1500] --out mesh.ply [--trunc T] [--view-step S] ...
   python tools/extract_mesh.py --tsdf CKPT.tar --datadir SCENE [--factor 4] --out mesh.ply [--trunc T] [--view-step S] ...
 
@@ -24,6 +25,12 @@ the faces that win a pixel in at least one of them, with the vertices those face
 of a sigma level set go.  It comes last, after the clean-up.  The cameras are those of --tsdf; without --tsdf they are read
 from --datadir / --factor.  Without the flag the file is what it was.
 
+--report-error prints what the clean-up cost: the distance report of the finished mesh (after --smooth, --simplify and
+--drop-unseen) against the mesh as first extracted (evaluate.mesh_distance_metrics, csrc/mesh_distance.hip: Chamfer and sampled
+Hausdorff distance, precision / recall / F-score at half a, one and two lattice steps, normal consistency), as one line
+`error report: {JSON}` in world units, with the largest lattice step under "lattice_step".  It changes no file; without the
+flag the tool's output is what it was.
+
 --texture N bakes a texture atlas of N texels along every face's leg (1..32) from the training views (mesh.bake_texture,
 csrc/texture.hip) and writes Wavefront OBJ + MTL + PNG; --out must end in .obj.  It comes after all clean-up and after
 --drop-unseen, so it textures the mesh that is written.  The images are renders of the field at the training cameras
@@ -39,6 +46,7 @@ over the observed cells; --threshold is not used.  It needs the cameras, taken t
 (mesh.frustum_bounds).  Prints the observed share of the lattice and each stage's time.
 """
 import argparse
+import json
 import os
 import sys
 import time
@@ -51,7 +59,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-from mvip_nerf_amd import mesh, ops, run                                       # noqa: E402
+from mvip_nerf_amd import evaluate, mesh, ops, run                             # noqa: E402
 
 
 def model_args(n_importance):
@@ -100,6 +108,21 @@ def clean_up(a, m, lo, hi, res):
     print(f'{what}: {m.faces.shape[0]} triangles, {m.verts.shape[0]} vertices -> {out.faces.shape[0]} triangles, '
           f'{out.verts.shape[0]} vertices')
     return out, t
+
+
+def report_error(a, first, m, lo, hi, res):
+    """--report-error: the finished Mesh m against the Mesh `first` as extracted, printed as one JSON line."""
+    if not a.report_error:
+        return
+    res3 = (res,) * 3 if np.isscalar(res) else tuple(res)
+    lo32, hi32 = mesh._bounds(lo, hi)
+    h = max(float((hi32[k] - lo32[k]) / np.float32(res3[k] - 1)) for k in range(3))
+    if not m.faces.shape[0] or not first.faces.shape[0]:
+        print('error report: null  (a mesh without faces)')
+        return
+    rep = evaluate.mesh_distance_metrics(m, first, samples=2, thresholds=(0.5 * h, h, 2.0 * h))
+    rep['lattice_step'] = h
+    print('error report: ' + json.dumps(rep))
 
 
 def drop_unseen(a, m, hwf, poses):
@@ -184,8 +207,10 @@ def main_tsdf(ap, a, res, dev):
         print(f'components of the inside points: {n_before} -> {n_after} kept')
     (verts, faces, normals), t_mc = _timed(lambda: mesh.marching_cubes(g, 1.0, lo32, hi32, valid=valid))
     colors, t_col = (None, 0.0) if a.no_colors else _timed(lambda: mesh.vertex_colors(te, verts, normals, a.network))
-    m, t_clean = clean_up(a, mesh.Mesh(verts, faces, normals, colors), lo32, hi32, res)
+    first = mesh.Mesh(verts, faces, normals, colors)
+    m, t_clean = clean_up(a, first, lo32, hi32, res)
     m, t_seen = drop_unseen(a, m, hwf, poses)
+    report_error(a, first, m, lo32, hi32, res)
     t_tex, t_ply = write_mesh(a, m, te, hwf, poses, near, far, dataset)
     print(f'tsdf zero level set: {m.verts.shape[0]} vertices, {m.faces.shape[0]} triangles -> {a.out}')
     print(f'time  model {t_model * 1e3:.1f} ms  render {t_render * 1e3:.1f} ms  fusion {t_fuse * 1e3:.1f} ms  components {t_cc * 1e3:.1f} ms  '
@@ -219,6 +244,8 @@ def main(argv=None):
                     help='bake a texture atlas of N texels per face leg from the training views and write OBJ + MTL + PNG (0: off)')
     ap.add_argument('--texture-from', choices=('render', 'dataset'), default='render',
                     help='--texture: the images are renders of the field at the training cameras, or the dataset\'s')
+    ap.add_argument('--report-error', action='store_true',
+                    help='print the distance report of the finished mesh against the mesh as first extracted')
     ap.add_argument('--tsdf', action='store_true', help='fuse rendered depth maps instead of thresholding sigma')
     ap.add_argument('--fixture', action='store_true', help='--tsdf: train the scene-1 fixture and use its cameras')
     ap.add_argument('--iters', type=int, default=1500, help='training iterations of --fixture')
@@ -264,7 +291,8 @@ def main(argv=None):
         print(f'components of the inside points: {n_before} -> {n_after} kept')
     (verts, faces, normals), t_mc = timed(lambda: mesh.marching_cubes(grid, a.threshold, a.bound_min, a.bound_max))
     colors, t_col = (None, 0.0) if a.no_colors else timed(lambda: mesh.vertex_colors(kw, verts, normals, a.network))
-    m, t_clean = clean_up(a, mesh.Mesh(verts, faces, normals, colors), a.bound_min, a.bound_max, res)
+    first = mesh.Mesh(verts, faces, normals, colors)
+    m, t_clean = clean_up(a, first, a.bound_min, a.bound_max, res)
     t_seen, hwf, cam_poses, near, far, loaded = 0.0, None, None, None, None, None
     if a.drop_unseen or a.texture:
         from mvip_nerf_amd.load_llff import load_llff_data
@@ -274,6 +302,7 @@ def main(argv=None):
         near, far = float(bds.min() * .9), float(bds.max() * 1.)
     if a.drop_unseen:
         m, t_seen = drop_unseen(a, m, hwf, cam_poses)
+    report_error(a, first, m, a.bound_min, a.bound_max, res)
     t_tex, t_ply = write_mesh(a, m, kw, hwf, cam_poses, near, far, lambda: loaded[0])
     print(f'threshold {a.threshold}: {m.verts.shape[0]} vertices, {m.faces.shape[0]} triangles -> {a.out}')
     print(f'time  density grid {t_grid * 1e3:.1f} ms  components {t_cc * 1e3:.1f} ms  marching cubes {t_mc * 1e3:.1f} ms  colours {t_col * 1e3:.1f} ms  '
