@@ -1131,6 +1131,34 @@ int mvip_mesh_distance_query(const float *points, int64_t n_points, const float 
 int mvip_mesh_sample_faces(const float *verts, const int *faces, int64_t n_verts, int64_t n_faces, int k, float *points,
                            int *face_of_sample, double *weights, int *flag, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Quantile termination depth of a ray, and agreement / free-space violations of depth maps across views (beyond the
+ * reference, which renders only the expected depth and never compares views: no entry point has a reference call site;
+ * csrc/ray_depth.hip, csrc/depth_consistency.hip, ops.ray_quantile_depth / depth_consistency, prepare.consistency_mask).
+ * One launch each on the caller's stream, no atomics, bit-reproducible.
+ * mvip_ray_quantile_depth: z [B,S] ascending along the ray and weights [B,S] DEVICE, levels[Q] HOST, depth [B,Q] DEVICE.
+ *   Per ray and level q, in integers and fp64 (shared word for word with tests/ray_depth_numpy.py):
+ *     Lq = (int64) floor((double) q 2^40);  W_j = (int64) floor(clamp((double) w_j, 0, 1) 2^40);  C_j = sum_{i<=j} W_i, C_{-1} = 0;
+ *     k = the smallest j with C_j >= Lq.  No k: depth = +inf.  k = S-1: depth = z_{S-1}.  Otherwise
+ *     f = (double)(Lq - C_{k-1}) / (double) W_k;  depth = (float)((double) z_k + f * ((double) z_{k+1} - (double) z_k)).
+ *   A ray with any non-finite weight gets NaN at every level; a non-finite z at the crossing propagates by the arithmetic; a
+ *   ray's result does not depend on B or its neighbours.  MVIP_EINVAL before anything is touched for: B < 0, S outside
+ *   1..4096, B S > 2^31 - 1, Q outside 1..8, levels NULL, a level outside 0 < q < 1 or with Lq < 1, a NULL device operand
+ *   while B > 0.  B = 0: MVIP_OK, no launch.
+ * mvip_depth_consistency: disp [V,H,W] fp32 (1 / planar depth), pose [V,3,4] camera-to-world (the camera of mvip_warp_views:
+ *   no half-pixel offset, looking down -z), agree / violated [V,H,W] int32, every element written.  In fp64 on the fp32
+ *   inputs, with mvip_warp_views' expressions (written out in csrc/depth_consistency.hip and
+ *   tests/depth_consistency_numpy.py): a pixel of view n with a finite disparity > 0 is lifted to its world point and
+ *   projected into every other view s (t_s, u, v); where t_s > 0, 0 <= u <= W-1, 0 <= v <= H-1 and all four bilinear taps
+ *   of view s are finite and > 0, resid = t_s d_s - 1 with d_s the bilinear disparity; agree counts the views with
+ *   |resid| <= tol, violated those with resid < -tol (resid > tol: occluded, nothing counted).  Other pixels get 0 / 0.
+ *   MVIP_EINVAL for: V < 0, H or W outside 2..16384, focal or tol not finite and > 0, a grid beyond 2^31 - 1 workgroups, a
+ *   NULL operand while V > 0.  V = 0: MVIP_OK, no launch; V = 1: all zeros. */
+int mvip_ray_quantile_depth(const float *z, const float *weights, int64_t B, int S, const float *levels, int Q, float *depth,
+                            void *stream);
+int mvip_depth_consistency(const float *disp, const float *pose, int V, int H, int W, float focal, float tol, int *agree,
+                           int *violated, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

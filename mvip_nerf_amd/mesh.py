@@ -486,16 +486,61 @@ def fuse_depths(disp, poses, focal, bound_min, bound_max, resolution=256, trunc=
     return Mesh(verts, faces, normals, None)
 
 
+SPREAD_LEVELS = (0.16, 0.5, 0.84)          # the quantiles behind max_spread: (z(0.84) - z(0.16)) / z(0.5)
+
+
+def filtered_disparities(render_kwargs, hwf, poses, near, far, chunk=1 << 15, depth='expected', max_spread=None, min_agree=None,
+                         max_violated=None, masks=None, tol=0.05):
+    """(disp [V, H, W], poses [V, 3, 4] fp32 on disp's device, masks [V, H, W] bool or None, shares): what extract_mesh_tsdf
+    hands to fuse_depths.  depth='expected': prepare.render_disparities; 'median': 1 / the median termination depth.
+    max_spread=r keeps the pixels whose quantiles z(0.16), z(0.5), z(0.84) are finite with (z(0.84) - z(0.16)) / z(0.5) <= r
+    (prepare.spread_mask); min_agree / max_violated keep those of prepare.consistency_mask of `disp` (a bound left None does
+    not filter).  The filters are computed independently of one another and ANDed with `masks`; with none of them `masks`
+    comes back as it is.  shares: per filter the share of pixels it masks ('spread', 'consistency'), for the record."""
+    from . import prepare
+    prepare._depth_kind('filtered_disparities', depth)
+    depth_q = None
+    if depth == 'median' or max_spread is not None:
+        levels = SPREAD_LEVELS if max_spread is not None else (0.5,)
+        depth_q = prepare.render_depth_quantiles(render_kwargs, hwf, poses, near, far, levels, chunk)
+    if depth == 'median':
+        disp = (1.0 / depth_q[..., levels.index(0.5)]).contiguous()
+    else:
+        disp = prepare.render_disparities(render_kwargs, hwf, poses, near, far, chunk=chunk)
+    poses = torch.as_tensor(poses).to(device=disp.device, dtype=torch.float32)[:, :3, :4].contiguous()
+    shares = {}
+    keep = None
+    if masks is not None:
+        keep = torch.as_tensor(masks).to(disp.device) != 0
+    if max_spread is not None:
+        m = prepare.spread_mask(depth_q, max_spread)
+        shares['spread'] = float((~m).float().mean().cpu()) if m.numel() else 0.0
+        keep = m if keep is None else keep & m
+    if min_agree is not None or max_violated is not None:
+        m = prepare.consistency_mask(disp, poses, float(hwf[2]), tol=tol, min_agree=0 if min_agree is None else min_agree,
+                                     max_violated=2 ** 31 - 1 if max_violated is None else max_violated)
+        shares['consistency'] = float((~m).float().mean().cpu()) if m.numel() else 0.0
+        keep = m if keep is None else keep & m
+    if keep is None or (max_spread is None and min_agree is None and max_violated is None):
+        return disp, poses, masks, shares
+    return disp, poses, keep.contiguous(), shares
+
+
 def extract_mesh_tsdf(render_kwargs, hwf, poses, near, far, bound_min, bound_max, resolution=256, trunc=None, colors=True,
-                      network='fine', chunk=1 << 15, largest=None, min_points=None, masks=None):
+                      network='fine', chunk=1 << 15, largest=None, min_points=None, masks=None, depth='expected', max_spread=None,
+                      min_agree=None, max_violated=None):
     """Mesh of what the renderer sees rather than of what the network stores: prepare.render_disparities of every pose
     [V, 3, 4] (hwf = (H, W, focal); `chunk` rays at a time), fuse_depths() of those maps, colours from vertex_colors()
     (uint8 [V, 3]) or None with colors=False.  Compositing has integrated the fog along each ray away and the average over
-    the views removes view-dependent floaters, so no sigma threshold is chosen.  Refuses NDC models (ValueError)."""
-    from . import prepare
+    the views removes view-dependent floaters, so no sigma threshold is chosen.  Refuses NDC models (ValueError).
+
+    depth / max_spread / min_agree / max_violated (defaults: today's result bit for bit) choose and filter the maps that are
+    fused, filtered_disparities(): depth='median' fuses the median termination depth, which lies on a surface where the
+    expected depth lies between two; max_spread drops the pixels whose ray does not see one surface; min_agree / max_violated
+    drop those no other view confirms / another view sees through."""
     _network(render_kwargs, network)
-    disp = prepare.render_disparities(render_kwargs, hwf, poses, near, far, chunk=chunk)
-    poses = torch.as_tensor(poses).to(device=disp.device, dtype=torch.float32)[:, :3, :4].contiguous()
+    disp, poses, masks, _ = filtered_disparities(render_kwargs, hwf, poses, near, far, chunk, depth, max_spread, min_agree,
+                                                 max_violated, masks)
     m = fuse_depths(disp, poses, float(hwf[2]), bound_min, bound_max, resolution, trunc, masks, largest, min_points)
     rgb = vertex_colors(render_kwargs, m.verts, m.normals, network) if colors else None
     return Mesh(m.verts, m.faces, m.normals, rgb)

@@ -2293,6 +2293,90 @@ def tsdf_fuse(disp, poses, focal, bound_min, bound_max, resolution, trunc, masks
     return tsdf, count
 
 
+# quantile ray depth and cross-view depth consistency (beyond the reference; csrc/ray_depth.hip, csrc/depth_consistency.hip) -------
+
+RAY_DEPTH_MAX_SAMPLES = 4096
+RAY_DEPTH_MAX_LEVELS = 8
+RAY_DEPTH_FIX = 2.0 ** 40          # weights and levels are compared as integers in units of 2^-40
+
+
+def _quantile_levels(what, levels):
+    import ctypes
+    import numpy as np
+    try:
+        lv = [float(np.float32(q)) for q in levels]
+    except TypeError:
+        raise ValueError(f'{what}: levels must be a sequence of numbers, got {type(levels).__name__}') from None
+    if not 1 <= len(lv) <= RAY_DEPTH_MAX_LEVELS:
+        raise ValueError(f'{what}: 1..{RAY_DEPTH_MAX_LEVELS} levels expected, got {len(lv)}')
+    if not all(0.0 < q < 1.0 and int(np.floor(q * RAY_DEPTH_FIX)) >= 1 for q in lv):
+        raise ValueError(f'{what}: every level must satisfy 0 < q < 1 (and q >= 2^-40), got {tuple(levels)}')
+    return (ctypes.c_float * len(lv))(*lv)
+
+
+def ray_quantile_depth(weights, z, levels=(0.5,)):
+    """depth [B, Q] fp32: per ray and level q the depth at which the accumulated compositing weight reaches q (q = 0.5: the
+    median termination depth), weights [B, S] and z [B, S] ascending along the ray, 1 <= S <= 4096, up to 8 levels (the
+    definition, in integers and fp64, is csrc/ray_depth.hip's and tests/ray_depth_numpy.py's).  +inf where the ray's weights
+    never sum to q; the last sample's own depth when it is the crossing one; NaN at every level of a ray with a non-finite
+    weight.  One launch for all levels.  Detached: no autograd."""
+    what = 'ray_quantile_depth'
+    if not (torch.is_tensor(weights) and torch.is_tensor(z)) or z.dim() != 2 or tuple(weights.shape) != tuple(z.shape) \
+            or not 1 <= z.shape[1] <= RAY_DEPTH_MAX_SAMPLES:
+        shape = lambda t: tuple(t.shape) if torch.is_tensor(t) else type(t).__name__
+        raise _lib.MvipError(f'{what}: weights {shape(weights)}, z {shape(z)}: two [B, S] tensors with 1 <= S <= '
+                             f'{RAY_DEPTH_MAX_SAMPLES} expected')
+    lv = _quantile_levels(what, levels)
+    if not (weights.is_cuda and z.device == weights.device):
+        raise _lib.MvipError(f'{what}: weights on {weights.device}, z on {z.device}; the HIP path has no CPU fallback')
+    B, S = z.shape
+    if B * S > 2 ** 31 - 1:
+        raise _lib.MvipError(f'{what}: {B} x {S} samples are beyond the kernel\'s index range')
+    w, zz = _f32c(weights.detach()), _f32c(z.detach())
+    depth = torch.empty((B, len(lv)), device=z.device, dtype=_F32)
+    call('mvip_ray_quantile_depth', ptr(zz), ptr(w), B, S, lv, len(lv), ptr(depth), stream())
+    return depth
+
+
+def depth_consistency(disp, poses, focal, masks=None, tol=0.05):
+    """(agree, violated), int32 [V, H, W]: per pixel of every view the number of OTHER views that see a surface at the
+    pixel's world point (|t_s d_s - 1| <= tol) and the number that see through it to a farther surface (t_s d_s - 1 < -tol: a
+    free-space violation, what a floater earns); an occluded point (residual > tol), one outside the other image or one
+    that lands on an invalid pixel counts as neither.  disp [V, H, W] fp32 (1 / planar depth), poses [V, 3, 4]
+    camera-to-world, masks [V, H, W] bool or None: a False pixel is zeroed before the launch, so it is neither judged nor a
+    witness.  The definition (fp64, the conventions and the default tol of warp_views) is csrc/depth_consistency.hip's and
+    tests/depth_consistency_numpy.py's.  One launch.  Detached."""
+    what = 'depth_consistency'
+    d = _image_batch(what, disp, _F32, 'disp')
+    p = _pose_batch(what, poses, 'poses')
+    V, H, W = d.shape
+    if p.shape[0] != V:
+        raise ValueError(f'{what}: disp {tuple(d.shape)}, poses {tuple(p.shape)}: one V expected')
+    if H < 2 or W < 2 or H > RASTER_MAX_SIDE or W > RASTER_MAX_SIDE:
+        raise ValueError(f'{what}: images of 2..{RASTER_MAX_SIDE} pixels a side expected, got {H} x {W}')
+    focal, tol = float(focal), float(tol)
+    if not (0.0 < focal < float('inf') and 0.0 < tol < float('inf')):
+        raise ValueError(f'{what}: focal {focal} and tol {tol} must be finite and > 0')
+    tensors = [d, p]
+    m = None
+    if masks is not None:
+        m = _image_batch(what, masks, torch.bool, 'masks')
+        if tuple(m.shape) != (V, H, W):
+            raise ValueError(f'{what}: masks {tuple(m.shape)} for disp {tuple(d.shape)}')
+        tensors.append(m)
+    _on_gpu(what, *tensors)
+    if any(t.device != d.device for t in tensors):
+        raise ValueError(f'{what}: tensors on one device expected, got {sorted({str(t.device) for t in tensors})}')
+    if not all(t.is_contiguous() for t in tensors):
+        raise ValueError(f'{what}: every operand must be contiguous')
+    if m is not None:
+        d = torch.where(m, d, torch.zeros((), device=d.device, dtype=_F32)).contiguous()
+    agree = torch.empty((V, H, W), device=d.device, dtype=_I32)
+    violated = torch.empty((V, H, W), device=d.device, dtype=_I32)
+    call('mvip_depth_consistency', ptr(d), ptr(p), V, H, W, focal, tol, ptr(agree, _I32), ptr(violated, _I32), stream())
+    return agree, violated
+
+
 # structural similarity with its gradient (beyond the reference, whose evaluation.py takes its metrics from pyiqa; csrc/ssim.hip) --
 
 SSIM_WINDOW = 11                 # taps; the map is [N, H - 10, W - 10, C]

@@ -20,6 +20,11 @@ carried into every other view by backward depth warping (`ops.warp_views`), what
 and `write_images` writes the files.  The inpainted reference itself can be made here too: `inpaint_views` fills the masks of
 the reference views with texture from the same image (`ops.exemplar_fill`; plausible, not pixel-accurate),
 and `propagate_reference(..., fill='exemplar')` uses the same fill for what no reference sees.
+
+Which depth is rendered is a choice: `render_disparities(kind='median')` gives 1 / the median termination
+depth of each ray instead of 1 / the expected one, `render_depth_quantiles` several quantiles at once, `spread_mask` the pixels
+whose ray sees one thin surface and `consistency_mask` those that other views confirm and none sees through
+(`ops.ray_quantile_depth`, `ops.depth_consistency`).  Every default is the expected depth, unfiltered.
 """
 import os
 
@@ -36,13 +41,26 @@ def _poses(poses):
     return poses
 
 
-def render_disparities(render_kwargs, hwf, poses, near, far, chunk=1 << 15):
+DEPTH_KINDS = ('expected', 'median')
+
+
+def _depth_kind(who, kind):
+    if kind not in DEPTH_KINDS:
+        raise ValueError(f'{who}: kind must be one of {DEPTH_KINDS}, got {kind!r}')
+    return kind
+
+
+def render_disparities(render_kwargs, hwf, poses, near, far, chunk=1 << 15, kind='expected'):
     """float32 [N, H, W] on the device: `disp_map` of a no-grad `run.render` of each pose [N, 3, 4] (camera-to-world), through
     the route of region.propagate_masks; bit-equal to run.render(H, W, focal, chunk=chunk, c2w=pose, near=near, far=far,
-    **render_kwargs)[1]."""
+    **render_kwargs)[1].  kind='median': 1 / (the median termination depth of the ray) instead, render_depth_quantiles at
+    level 0.5 -- 0 where the ray never accumulates half (the median is +inf), NaN where it is NaN; between two surfaces the
+    expected depth lies where nothing is, the median on one of them."""
     from . import run
     H, W, focal = int(hwf[0]), int(hwf[1]), float(hwf[2])
     poses = _poses(poses)
+    if _depth_kind('render_disparities', kind) == 'median':
+        return (1.0 / render_depth_quantiles(render_kwargs, hwf, poses, near, far, (0.5,), chunk)[..., 0]).contiguous()
     kw = dict(render_kwargs, near=near, far=far)
     out = []
     with torch.no_grad():
@@ -53,10 +71,58 @@ def render_disparities(render_kwargs, hwf, poses, near, far, chunk=1 << 15):
     return torch.stack(out, 0).contiguous()
 
 
-def prepare_depths(render_kwargs, hwf, poses, masks, near, far, dilate=0, chunk=1 << 15, allow_unconverged=False, **fill_kw):
+def render_depth_quantiles(render_kwargs, hwf, poses, near, far, levels=(0.16, 0.5, 0.84), chunk=1 << 15):
+    """float32 [N, H, W, Q] on the device: the 'depth_q' extra of a no-grad `run.render(..., depth_quantiles=levels)` of each
+    pose: per pixel the depths at which the ray's accumulated weight reaches each level (ops.ray_quantile_depth; +inf where it
+    never does).  The default levels give the median and, as z(0.84) - z(0.16), a thickness: how far the ray is from seeing
+    one surface."""
+    from . import run
+    H, W, focal = int(hwf[0]), int(hwf[1]), float(hwf[2])
+    poses = _poses(poses)
+    levels = tuple(levels)
+    kw = dict(render_kwargs, near=near, far=far, depth_quantiles=levels)
+    out = []
+    with torch.no_grad():
+        for c2w in poses:
+            out.append(run.render(H, W, focal, chunk=int(chunk), c2w=c2w, **kw)[4]['depth_q'])
+    if not out:
+        return torch.empty((0, H, W, len(levels)), device=poses.device if poses.is_cuda else 'cuda', dtype=torch.float32)
+    return torch.stack(out, 0).contiguous()
+
+
+def spread_mask(depth_q, max_spread):
+    """bool [N, H, W]: the pixels of depth_q [N, H, W, 3] (levels low < mid < high, e.g. render_depth_quantiles' default) whose
+    three quantiles are finite and whose relative thickness (z_high - z_low) / z_mid is <= max_spread."""
+    if not torch.is_tensor(depth_q) or depth_q.dim() != 4 or depth_q.shape[-1] != 3:
+        raise ValueError(f'spread_mask: depth_q [N, H, W, 3] expected, got '
+                         f'{tuple(depth_q.shape) if torch.is_tensor(depth_q) else type(depth_q).__name__}')
+    max_spread = float(max_spread)
+    if not 0.0 <= max_spread < float('inf'):
+        raise ValueError(f'spread_mask: max_spread must be finite and >= 0, got {max_spread}')
+    lo, mid, hi = depth_q[..., 0], depth_q[..., 1], depth_q[..., 2]
+    return torch.isfinite(depth_q).all(-1) & ((hi - lo) / mid <= max_spread)
+
+
+def consistency_mask(disp, poses, focal, tol=0.05, min_agree=1, max_violated=0, masks=None):
+    """bool [N, H, W]: the pixels of disp [N, H, W] that at least `min_agree` other views confirm and at most `max_violated`
+    other views see through (ops.depth_consistency; `masks` as there).  The defaults keep what one other camera has seen
+    at the same place and no camera has seen through.  A pixel without a finite disparity > 0 counts 0 / 0."""
+    min_agree, max_violated = int(min_agree), int(max_violated)
+    if min_agree < 0 or max_violated < 0:
+        raise ValueError(f'consistency_mask: min_agree {min_agree} and max_violated {max_violated} must be >= 0')
+    poses = _poses(poses)
+    if torch.is_tensor(disp) and poses.device != disp.device:
+        poses = poses.to(disp.device)
+    agree, violated = ops.depth_consistency(disp, poses.to(torch.float32).contiguous(), focal, masks=masks, tol=tol)
+    return (agree >= min_agree) & (violated <= max_violated)
+
+
+def prepare_depths(render_kwargs, hwf, poses, masks, near, far, dilate=0, chunk=1 << 15, allow_unconverged=False, kind='expected',
+                   **fill_kw):
     """Render the disparity of every pose and fill the masked pixels harmonically.  masks [N, H, W] bool (tensor or array);
     `dilate` rounds of ops.mask_dilate2d are applied first (a generous mask keeps the object's rim out of the boundary
-    values); fill_kw goes to ops.harmonic_fill (eps, max_iters, check_every).
+    values); fill_kw goes to ops.harmonic_fill (eps, max_iters, check_every); `kind` is render_disparities' ('median': the
+    median termination depth instead of the expected one).
 
     Returns dict(disp [N, H, W] the rendered disparity, filled [N, H, W], masks [N, H, W] bool: the dilated set that was
     filled, info: ops.harmonic_fill's).  Non-finite rendered pixels are filled too.  ValueError for a singular view (every
@@ -64,7 +130,10 @@ def prepare_depths(render_kwargs, hwf, poses, masks, near, far, dilate=0, chunk=
     max_iters, unless allow_unconverged."""
     H, W = int(hwf[0]), int(hwf[1])
     poses = _poses(poses)
-    disp = render_disparities(render_kwargs, hwf, poses, near, far, chunk)
+    if _depth_kind('prepare_depths', kind) == 'expected':
+        disp = render_disparities(render_kwargs, hwf, poses, near, far, chunk)
+    else:
+        disp = render_disparities(render_kwargs, hwf, poses, near, far, chunk, kind=kind)
     masks = torch.as_tensor(np.asarray(masks) if not torch.is_tensor(masks) else masks)
     if tuple(masks.shape) != (poses.shape[0], H, W):
         raise ValueError(f'masks [{poses.shape[0]}, {H}, {W}] expected, got {tuple(masks.shape)}')

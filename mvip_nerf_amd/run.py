@@ -170,7 +170,7 @@ FUSED_RENDER_MAX_RAYS = int(os.environ.get('MVIP_FUSED_RENDER_MAX_RAYS', '4096')
 def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False, lindisp=False, perturb=0.,
                 N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0., pytest=False,
                 sigma_loss=None, verbose=False, need_alpha=False, detach_weights=False, coarse_grad=True, occupancy=None,
-                region=None, distortion=False):
+                region=None, distortion=False, depth_quantiles=None):
     """DS_NeRF/run.py:1703-1847: stratified depths -> coarse MLP -> compositing -> inverse-CDF
     resampling + merge -> fine MLP -> compositing.  Five kernel launches per chunk on the native
     path (z, MLP, composite, sample+merge, MLP, composite) instead of ~150 torch ops.
@@ -195,7 +195,12 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
     'dist_loss0' [B], the same of the coarse pass's (as rgb0 mirrors rgb_map); both with this call's `lindisp`, each carrying
     whatever gradient its weights carry (dist_loss0 none under coarse_grad=False).  The two-launch route does not expose the
     coarse weights, so the call takes the six-launch chain (bit-identical).  ValueError together with `occupancy`: it is a
-    training loss, like sigma_loss."""
+    training loss, like sigma_loss.
+
+    `depth_quantiles` (extension, default None = no launch and no key added): a tuple of levels 0 < q < 1; the returned dict
+    gains 'depth_q' [B, Q], ops.ray_quantile_depth of the FINAL pass's `weights` / `z_vals` (q = 0.5: the median termination
+    depth; +inf where the ray never accumulates q), one launch on this call's own outputs whichever route produced them,
+    `occupancy` included.  It carries no gradient."""
     ray_batch = ray_batch.float() if ray_batch.dtype != torch.float32 else ray_batch
     ray_batch = ray_batch.contiguous()
     N_rays, ncols = ray_batch.shape
@@ -234,6 +239,8 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
                                      need_alpha, detach_weights, t_rand)
         if region is not None:
             ret['region_map'] = region.accumulate(rows, ret['z_vals'], ret['weights'])
+        if depth_quantiles is not None:
+            ret['depth_q'] = ops.ray_quantile_depth(ret['weights'], ret['z_vals'], depth_quantiles)
         return ret
     if (FUSED_RENDER and not distortion and not torch.is_grad_enabled() and 0 < N_rays <= FUSED_RENDER_MAX_RAYS and N_samples == 64 and 0 < N_importance <= 64
             and ncols == 11 and sigma_loss is None and getattr(network_query_fn, '_mvip_native', False)
@@ -258,6 +265,8 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
             ret['rgb0'], ret['disp0'], ret['acc0'], ret['z_std'] = rgb0, disp0, acc0, z_std
             if region is not None:
                 ret['region_map'] = region.accumulate(rows, z_vals, weights)
+            if depth_quantiles is not None:
+                ret['depth_q'] = ops.ray_quantile_depth(weights, z_vals, depth_quantiles)
             return ret
     z_vals = ops.stratified_z(rows, N_samples, lindisp, t_rand)
 
@@ -302,6 +311,8 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
         ret['dist_loss'] = ops.distortion_loss(weights, z_vals, bounds, lindisp)
         if N_importance > 0:
             ret['dist_loss0'] = ops.distortion_loss(weights_0, z_vals_0, bounds, lindisp)
+    if depth_quantiles is not None:
+        ret['depth_q'] = ops.ray_quantile_depth(weights, z_vals, depth_quantiles)
     if DEBUG:
         for k in ret:
             if torch.isnan(ret[k]).any() or torch.isinf(ret[k]).any():

@@ -189,15 +189,21 @@ def main_tsdf(ap, a, res, dev):
     if (a.bound_min is None) != (a.bound_max is None):
         ap.error('--bound-min and --bound-max come together')
     lo, hi = (a.bound_min, a.bound_max) if a.bound_min is not None else mesh.frustum_bounds(poses, hwf, near, far)
-    disp, t_render = _timed(lambda: prepare.render_disparities(te, hwf, poses, near, far))
+    if (a.max_spread is not None and not a.max_spread >= 0) or (a.min_agree is not None and a.min_agree < 0) \
+            or (a.max_violated is not None and a.max_violated < 0):
+        ap.error('--max-spread, --min-agree and --max-violated must be >= 0')
+    (disp, poses, keep, shares), t_render = _timed(lambda: mesh.filtered_disparities(
+        te, hwf, poses, near, far, depth=a.tsdf_depth, max_spread=a.max_spread, min_agree=a.min_agree, max_violated=a.max_violated))
     lo32, hi32 = mesh._bounds(lo, hi)
     res3 = (res,) * 3 if np.isscalar(res) else tuple(res)
     trunc = a.trunc if a.trunc is not None else 4.0 * max(float((hi32[k] - lo32[k]) / np.float32(res3[k] - 1)) for k in range(3))
-    (tsdf, count), t_fuse = _timed(lambda: ops.tsdf_fuse(disp, poses, hwf[2], lo32, hi32, res3, trunc))
+    (tsdf, count), t_fuse = _timed(lambda: ops.tsdf_fuse(disp, poses, hwf[2], lo32, hi32, res3, trunc, masks=keep))
     valid = count > 0
     g = torch.where(valid, 1.0 - tsdf, torch.zeros((), device=dev))
     print(f'{source}: {poses.shape[0]} views of {hwf[0]} x {hwf[1]}, lattice {tuple(tsdf.shape)} in {[round(float(v), 4) for v in lo32]} .. '
           f'{[round(float(v), 4) for v in hi32]}, trunc {trunc:.4g}')
+    if a.tsdf_depth != 'expected' or shares:
+        print(f'depth maps: {a.tsdf_depth}' + ''.join(f', {k} filter masks {v:.4f} of the pixels' for k, v in shares.items()))
     print(f'observed share of the lattice {float(valid.float().mean()):.4f}  (inside: {float((valid & (tsdf <= 0)).float().mean()):.4f})')
     t_cc = 0.0
     if a.keep_largest is not None or a.min_component is not None:
@@ -253,6 +259,14 @@ def main(argv=None):
     ap.add_argument('--factor', type=int, default=4)
     ap.add_argument('--trunc', type=float, default=None, help='--tsdf: truncation distance (default: 4 lattice steps)')
     ap.add_argument('--view-step', type=int, default=1, metavar='S', help='--tsdf: fuse every S-th view')
+    ap.add_argument('--tsdf-depth', choices=('expected', 'median'), default='expected',
+                    help='--tsdf: fuse the expected ray depth (default) or the median termination depth')
+    ap.add_argument('--max-spread', type=float, default=None, metavar='R',
+                    help='--tsdf: drop the pixels whose ray has (z(0.84) - z(0.16)) / z(0.5) > R (default: off; tools/depth_quality.py '
+                         'suggests a value)')
+    ap.add_argument('--min-agree', type=int, default=None, metavar='K', help='--tsdf: drop the pixels fewer than K other views confirm')
+    ap.add_argument('--max-violated', type=int, default=None, metavar='K',
+                    help='--tsdf: drop the pixels more than K other views see through')
     a = ap.parse_args(argv)
     if a.smooth < 0 or not a.simplify >= 0:
         ap.error('--smooth and --simplify must be >= 0')

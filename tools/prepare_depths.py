@@ -42,6 +42,8 @@ def main(argv=None):
     ap.add_argument('--dilate', type=int, default=0, help='rounds of 2D dilation of the masks before the fill')
     ap.add_argument('--eps', type=float, default=1e-7)
     ap.add_argument('--max-iters', type=int, default=None)
+    ap.add_argument('--depth', choices=('expected', 'median'), default='expected',
+                    help='render the expected ray depth (default) or the median termination depth')
     ap.add_argument('--out', required=True)
     a = ap.parse_args(argv)
     if a.fixture == bool(a.checkpoint) or bool(a.checkpoint) != bool(a.datadir):
@@ -62,7 +64,7 @@ def main(argv=None):
     if not valid.all():
         raise SystemExit(f'views {np.nonzero(~valid)[0].tolist()} have no mask')
     os.makedirs(a.out, exist_ok=True)
-    disp, t_render = timed(lambda: prepare.render_disparities(te, hwf, poses, near, far))
+    disp, t_render = timed(lambda: prepare.render_disparities(te, hwf, poses, near, far, kind=a.depth))
     dil, t_dilate = timed(lambda: ops.mask_dilate2d(torch.from_numpy(masks).to(dev), a.dilate))
     (filled, info), t_fill = timed(lambda: ops.harmonic_fill(disp, dil, eps=a.eps, max_iters=a.max_iters))
     if info['singular'].any() or not info['converged'].all():
@@ -72,7 +74,7 @@ def main(argv=None):
     clipped, t_write = timed(lambda: prepare.write_llff(a.out, names, m_np, f_np))
     np.save(os.path.join(a.out, 'filled.npy'), f_np)
     total = t_render + t_dilate + t_fill + t_write
-    out = {'source': source, 'frame': [hwf[0], hwf[1]], 'views': len(names), 'dilate': a.dilate, 'eps': a.eps,
+    out = {'source': source, 'frame': [hwf[0], hwf[1]], 'views': len(names), 'dilate': a.dilate, 'eps': a.eps, 'depth': a.depth,
            'mask_share_of_frame': float(masks.mean()), 'filled_share_of_frame': float(m_np.mean()),
            'unknowns_per_view': info['unknowns'].tolist(), 'iterations_per_view': info['iterations'].tolist(),
            'true_residual_per_view': [float(r) for r in info['residual']], 'clipped_pixels': clipped,
