@@ -5,13 +5,11 @@
 // tests/raster_numpy.py.  Everything is fp64 and integers (built with -ffp-contract=off; fp64 + - * / and rint are correctly
 // rounded), so the restatement agrees BIT FOR BIT.
 //
-// Conventions (those of csrc/tsdf.hip and csrc/warp.hip): c2w [3, 4] row-major = [R | o], the camera looks down -z, no
-// half-pixel offset (pixel (x, y) is the sample point u = x, w = y), disparity = 1 / planar depth, faces counter-clockwise seen
-// from outside (csrc/mcubes.hip).
+// The camera and its project are csrc/camera_device.h's, here with T = double; faces are counter-clockwise seen from outside
+// (csrc/mcubes.hip).
 //
-// Per view, per vertex p (fp32 widened to fp64, this operation order):
-//   dl = p - o;  q[j] = (R[0][j] dl[0] + R[1][j] dl[1]) + R[2][j] dl[2];  z = -q[2]
-//   u = (f q[0]) / z + W/2;  w = -((f q[1]) / z) + H/2;  d = 1 / z
+// Per view, per vertex p (fp32 widened to fp64):
+//   (u, w, z) = project(pose, p);  d = 1 / z
 //   X = rint(256 u), Y = rint(256 w)                  8 sub-pixel bits, ties to even, integers from here on
 // Per face: dropped whole for the view unless every vertex has z >= near and |256 u|, |256 w| <= 2^22 (compared in fp64 before
 // the conversion; a NaN fails).  The bound is a guard band of 16,384 pixels (the largest image side), which keeps every edge
@@ -212,15 +210,13 @@ __global__ __launch_bounds__(BLOCK) void resolve_kernel(const unsigned long long
     }
 }
 
-static inline bool positive_finite(double x) { return x > 0.0 && x <= 1.7976931348623157e308; }
-
 // the checks the two entry points share; N = the pixels of all views
 static inline bool shape_ok(int64_t n_verts, int64_t n_faces, int64_t n_views, int H, int W, double focal, double znear,
                             long long &N) {
     if (n_verts < 0 || n_verts > INT_MAX64 || n_faces < 0 || 3 * n_faces > INT_MAX64 || n_views < 0 || n_views > INT_MAX64)
         return false;
     if (H < 1 || W < 1 || H > MAX_SIDE || W > MAX_SIDE) return false;
-    if (!positive_finite(focal) || !positive_finite(znear)) return false;
+    if (!camera::usable(focal) || !camera::usable(znear)) return false;
     N = (long long)n_views * H * W;                         // < 2^31 * 2^28
     return (N + BLOCK - 1) / BLOCK <= INT_MAX64;
 }

@@ -1,15 +1,15 @@
-// The camera projection and the per-view set-up of a face, shared by the mesh rasteriser (csrc/raster.hip) and the mesh
-// texturing (csrc/texture.hip): ONE definition of how a world point lands in a view and of the integer edge functions of a
-// face there.  The definition is stated in the header comment of csrc/raster.hip (restated in tests/raster_numpy.py); every
-// expression below keeps its association (the library is built with -ffp-contract=off), so both files compute the same bits.
+// The per-view set-up of a face, shared by the mesh rasteriser (csrc/raster.hip) and the mesh texturing (csrc/texture.hip): ONE
+// definition of the sub-pixel position of a vertex in a view (the projection itself is csrc/camera_device.h's, in fp64) and of
+// the integer edge functions of a face there.  The definition is stated in the header comment of csrc/raster.hip (restated in
+// tests/raster_numpy.py); every expression below keeps its association (the library is built with -ffp-contract=off), so both
+// files compute the same bits.
 #pragma once
-#include "common.h"
-#include <math.h>
+#include "camera_device.h"
 
 namespace mvip {
 namespace raster {
 
-constexpr int MAX_SIDE = 16384;
+constexpr int MAX_SIDE = camera::MAX_SIDE;
 constexpr double BAND = 4194304.0;           // 2^22 sub-pixel units = 16,384 pixels
 
 struct Camera {
@@ -17,22 +17,10 @@ struct Camera {
     double f, cu, cw, znear;
 };
 
-// the continuous image position (u, w) and the planar depth z of the world point (p0, p1, p2); nothing is tested here
-__device__ __forceinline__ void project_point(const Camera &c, double p0, double p1, double p2, double &u, double &w, double &z) {
-    const float *__restrict__ P = c.P;
-    const double dl0 = p0 - (double)P[3], dl1 = p1 - (double)P[7], dl2 = p2 - (double)P[11];
-    const double q0 = ((double)P[0] * dl0 + (double)P[4] * dl1) + (double)P[8] * dl2;
-    const double q1 = ((double)P[1] * dl0 + (double)P[5] * dl1) + (double)P[9] * dl2;
-    const double q2 = ((double)P[2] * dl0 + (double)P[6] * dl1) + (double)P[10] * dl2;
-    z = -q2;
-    u = (c.f * q0) / z + c.cu;
-    w = -((c.f * q1) / z) + c.cw;
-}
-
 __device__ __forceinline__ bool project(const Camera &c, const float *__restrict__ verts, int i, int &X, int &Y, double &d) {
     const float *__restrict__ p = verts + 3 * (long long)i;
     double u, w, z;
-    project_point(c, (double)p[0], (double)p[1], (double)p[2], u, w, z);
+    camera::project<double>(c.P, c.f, c.cu, c.cw, (double)p[0], (double)p[1], (double)p[2], u, w, z);
     d = 1.0 / z;
     const double su = 256.0 * u, sw = 256.0 * w;
     const bool ok = z >= c.znear && fabs(su) <= BAND && fabs(sw) <= BAND;      // a NaN fails

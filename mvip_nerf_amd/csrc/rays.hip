@@ -1,16 +1,18 @@
 // Ray generation, ray-row assembly, stratified depths and the materialised sinusoidal encoding.
 // All HBM-bound, one element per thread, arithmetic written in the reference's operation order
 // (the library is built with -ffp-contract=off so a*b+c stays two roundings like torch's).
+#include "camera_device.h"
 #include "rays_device.h"
 #include <stdlib.h>
 
 namespace mvip {
 
-// dirs = ((x - W/2)/f, -(y - H/2)/f, -1); d[c] = sum_k dirs[k] * R[c][k]   (run_nerf_helpers.py:254-257)
+// dirs = camera::pixel_dir with its -1; d[c] = sum_k dirs[k] * R[c][k]   (run_nerf_helpers.py:254-257): the direction is rotated
+// before any depth is applied, which is another association than camera::unproject's
 __device__ __forceinline__ void pixel_ray(const float *__restrict__ c2w, int H, int W, float focal,
                                           int y, int x, float o[3], float d[3]) {
-    const float dx = ((float)x - (float)W * .5f) / focal;
-    const float dy = -(((float)y - (float)H * .5f) / focal);
+    float dx, dy;
+    camera::pixel_dir<float>(x, y, H, W, focal, dx, dy);
     const float dz = -1.0f;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {

@@ -27,7 +27,7 @@
 //   every texel of non-zero weight belongs to the face, and the owned sets are disjoint.
 //
 // BAKE of a sample point p with normal nrm (both fp64), views v = 0 .. V - 1 in ascending order.  View v contributes iff ALL of:
-//   projection  (u, w, z) = raster::project_point (raster_device.h: THE projection), z >= near
+//   projection  (u, w, z) = camera::project<double> (camera_device.h: THE projection), z >= near
 //   image       0 <= u <= W - 1 and 0 <= w <= H - 1
 //   facing      l = o - p, c = (nrm0 l0 + nrm1 l1) + nrm2 l2; cull 'back': c > 0, 'none': c > 0 or c < 0
 //   weight      nn = (nrm0^2 + nrm1^2) + nrm2^2 > 0, ll likewise, wgt = (c c) / (nn ll) finite and > 0    (cos^2 of incidence)
@@ -110,9 +110,8 @@ __device__ __forceinline__ void bake(const Views &vw, const double p0, const dou
     int bi = -1;
     for (int v = 0; v < vw.V; ++v) {
         const float *__restrict__ P = vw.poses + 12ll * v;
-        const rs::Camera cam{P, vw.f, (double)vw.W * 0.5, (double)vw.H * 0.5, vw.znear};
         double u, w, z;
-        rs::project_point(cam, p0, p1, p2, u, w, z);
+        camera::project<double>(P, vw.f, (double)vw.W * 0.5, (double)vw.H * 0.5, p0, p1, p2, u, w, z);
         if (!(z >= vw.znear && u >= 0.0 && u <= (double)(vw.W - 1) && w >= 0.0 && w <= (double)(vw.H - 1))) continue;
         const double l0 = (double)P[3] - p0, l1 = (double)P[7] - p1, l2 = (double)P[11] - p2;
         const double c = (n0 * l0 + n1 * l1) + n2 * l2;
@@ -120,6 +119,7 @@ __device__ __forceinline__ void bake(const Views &vw, const double p0, const dou
         const double ll = (l0 * l0 + l1 * l1) + l2 * l2;
         const double wgt = (c * c) / (nn * ll);
         if (!(nn > 0.0 && wgt > 0.0 && wgt <= DBL_MAX)) continue;
+        // the footprint clamps the UPPER corner (x1), so it also takes 1-pixel images: not camera::lower_footprint's rule
         const int x0 = (int)floor(u), y0 = (int)floor(w);                  // inside [0, W - 1] x [0, H - 1]
         const int x1 = min(x0 + 1, vw.W - 1), y1 = min(y0 + 1, vw.H - 1);
         const double fx = u - (double)x0, fy = w - (double)y0;
@@ -274,13 +274,11 @@ __global__ __launch_bounds__(BLOCK) void resolve_kernel(const int *__restrict__ 
     rgb[3 * n + 2] = out[2];
 }
 
-static inline bool positive_finite(double x) { return x > 0.0 && x <= DBL_MAX; }
-
 // the checks of the cameras and images that the entry points share
 static inline bool views_ok(int64_t n_views, int H, int W, double focal, double znear) {
     if (n_views < 0 || n_views > INT_MAX64) return false;
     if (H < 1 || W < 1 || H > rs::MAX_SIDE || W > rs::MAX_SIDE) return false;
-    return positive_finite(focal) && positive_finite(znear);
+    return camera::usable(focal) && camera::usable(znear);
 }
 
 static inline bool bake_ok(int64_t n_views, int H, int W, double focal, double znear, double tol, int cull, int mode) {

@@ -2194,6 +2194,34 @@ def _pose_batch(what, t, name):
     return t.detach()
 
 
+def _view_batch(what, disp, poses, masks):
+    """disp [V, H, W] fp32, poses [V, 3, 4] and the optional masks [V, H, W] bool of one V -> (d, p, m or None), detached."""
+    d = _image_batch(what, disp, _F32, 'disp')
+    p = _pose_batch(what, poses, 'poses')
+    if p.shape[0] != d.shape[0]:
+        raise ValueError(f'{what}: disp {tuple(d.shape)}, poses {tuple(p.shape)}: one V expected')
+    m = None
+    if masks is not None:
+        m = _image_batch(what, masks, torch.bool, 'masks')
+        if tuple(m.shape) != tuple(d.shape):
+            raise ValueError(f'{what}: masks {tuple(m.shape)} for disp {tuple(d.shape)}')
+    return d, p, m
+
+
+def _views_ready(what, tensors, **scalars):
+    """What every view operator checks last: the two scalars given by name (focal and the call's tolerance) finite and > 0,
+    the operands on one GPU and contiguous.  Returns the scalars as floats."""
+    (a, x), (b, y) = ((k, float(v)) for k, v in scalars.items())
+    if not (0.0 < x < float('inf') and 0.0 < y < float('inf')):
+        raise ValueError(f'{what}: {a} {x} and {b} {y} must be finite and > 0')
+    _on_gpu(what, *tensors)
+    if any(t.device != tensors[0].device for t in tensors):
+        raise ValueError(f'{what}: tensors on one device expected, got {sorted({str(t.device) for t in tensors})}')
+    if not all(t.is_contiguous() for t in tensors):
+        raise ValueError(f'{what}: every operand must be contiguous')
+    return x, y
+
+
 def warp_views(tgt_disp, tgt_pose, tgt_mask, src_rgb, src_disp, src_pose, focal, order=None, tol=0.05):
     """Backward depth warp of S source views into N target views (the definition is csrc/warp.hip's and tests/warp_numpy.py's).
     tgt_disp [N, H, W] fp32, tgt_pose [N, 3, 4], tgt_mask [N, H, W] bool (the pixels to compute); src_rgb [S, H, W, 3],
@@ -2220,20 +2248,13 @@ def warp_views(tgt_disp, tgt_pose, tgt_mask, src_rgb, src_disp, src_pose, focal,
                          f'{H} x {W}: one S, and the targets\' H, W expected')
     if H < 2 or W < 2:
         raise ValueError(f'{what}: images of at least 2 x 2 expected, got {H} x {W}')
-    focal, tol = float(focal), float(tol)
-    if not (0.0 < focal < float('inf') and 0.0 < tol < float('inf')):
-        raise ValueError(f'{what}: focal {focal} and tol {tol} must be finite and > 0')
     tensors = [d, tp, m, sc, sd, sp]
     if order is not None:
         if not torch.is_tensor(order) or order.dtype != _I32 or tuple(order.shape) != (N, S):
             got = f'{tuple(order.shape)} {order.dtype}' if torch.is_tensor(order) else type(order).__name__
             raise ValueError(f'{what}: order must be an {_I32} tensor [{N}, {S}] on the GPU, got {got}')
         tensors.append(order.detach())
-    _on_gpu(what, *tensors)
-    if any(t.device != d.device for t in tensors):
-        raise ValueError(f'{what}: tensors on one device expected, got {sorted({str(t.device) for t in tensors})}')
-    if not all(t.is_contiguous() for t in tensors):
-        raise ValueError(f'{what}: every operand must be contiguous')
+    focal, tol = _views_ready(what, tensors, focal=focal, tol=tol)
     if order is None:
         order = torch.arange(S, device=d.device, dtype=_I32).repeat(N, 1).reshape(N, S)
     rgb = torch.empty((N, H, W, 3), device=d.device, dtype=_F32)
@@ -2257,25 +2278,11 @@ def tsdf_fuse(disp, poses, focal, bound_min, bound_max, resolution, trunc, masks
     import math
     import numpy as np
     what = 'tsdf_fuse'
-    d = _image_batch(what, disp, _F32, 'disp')
-    p = _pose_batch(what, poses, 'poses')
+    d, p, m = _view_batch(what, disp, poses, masks)
     V, H, W = d.shape
-    if p.shape[0] != V:
-        raise ValueError(f'{what}: disp {tuple(d.shape)}, poses {tuple(p.shape)}: one V expected')
     if H < 1 or W < 1:
         raise ValueError(f'{what}: images of at least 1 x 1 expected, got {H} x {W}')
-    tensors = [d, p]
-    m = None
-    if masks is not None:
-        m = _image_batch(what, masks, torch.bool, 'masks')
-        if tuple(m.shape) != (V, H, W):
-            raise ValueError(f'{what}: masks {tuple(m.shape)} for disp {tuple(d.shape)}')
-        tensors.append(m)
-    _on_gpu(what, *tensors)
-    if any(t.device != d.device for t in tensors):
-        raise ValueError(f'{what}: tensors on one device expected, got {sorted({str(t.device) for t in tensors})}')
-    if not all(t.is_contiguous() for t in tensors):
-        raise ValueError(f'{what}: every operand must be contiguous')
+    focal, trunc = _views_ready(what, [d, p] if m is None else [d, p, m], focal=focal, trunc=trunc)
     lo = [float(np.float32(v)) for v in bound_min]
     hi = [float(np.float32(v)) for v in bound_max]
     if len(lo) != 3 or len(hi) != 3 or not all(math.isfinite(a) and math.isfinite(b) and a < b for a, b in zip(lo, hi)):
@@ -2283,9 +2290,6 @@ def tsdf_fuse(disp, poses, focal, bound_min, bound_max, resolution, trunc, masks
     res = (int(resolution),) * 3 if np.isscalar(resolution) else tuple(int(n) for n in resolution)
     if len(res) != 3 or not all(2 <= n <= MAX_COMPONENT_AXIS for n in res):
         raise ValueError(f'{what}: resolution {res}: three axes of 2..{MAX_COMPONENT_AXIS} points each')
-    focal, trunc = float(focal), float(trunc)
-    if not (0.0 < focal < float('inf') and 0.0 < trunc < float('inf')):
-        raise ValueError(f'{what}: focal {focal} and trunc {trunc} must be finite and > 0')
     tsdf = torch.empty(res, device=d.device, dtype=_F32)
     count = torch.empty(res, device=d.device, dtype=_I32)
     call('mvip_tsdf_fuse', ptr(d), ptr(p), ptr(m, torch.bool), V, H, W, focal, res[0], res[1], res[2], lo[0], lo[1], lo[2],
@@ -2347,28 +2351,11 @@ def depth_consistency(disp, poses, focal, masks=None, tol=0.05):
     witness.  The definition (fp64, the conventions and the default tol of warp_views) is csrc/depth_consistency.hip's and
     tests/depth_consistency_numpy.py's.  One launch.  Detached."""
     what = 'depth_consistency'
-    d = _image_batch(what, disp, _F32, 'disp')
-    p = _pose_batch(what, poses, 'poses')
+    d, p, m = _view_batch(what, disp, poses, masks)
     V, H, W = d.shape
-    if p.shape[0] != V:
-        raise ValueError(f'{what}: disp {tuple(d.shape)}, poses {tuple(p.shape)}: one V expected')
     if H < 2 or W < 2 or H > RASTER_MAX_SIDE or W > RASTER_MAX_SIDE:
         raise ValueError(f'{what}: images of 2..{RASTER_MAX_SIDE} pixels a side expected, got {H} x {W}')
-    focal, tol = float(focal), float(tol)
-    if not (0.0 < focal < float('inf') and 0.0 < tol < float('inf')):
-        raise ValueError(f'{what}: focal {focal} and tol {tol} must be finite and > 0')
-    tensors = [d, p]
-    m = None
-    if masks is not None:
-        m = _image_batch(what, masks, torch.bool, 'masks')
-        if tuple(m.shape) != (V, H, W):
-            raise ValueError(f'{what}: masks {tuple(m.shape)} for disp {tuple(d.shape)}')
-        tensors.append(m)
-    _on_gpu(what, *tensors)
-    if any(t.device != d.device for t in tensors):
-        raise ValueError(f'{what}: tensors on one device expected, got {sorted({str(t.device) for t in tensors})}')
-    if not all(t.is_contiguous() for t in tensors):
-        raise ValueError(f'{what}: every operand must be contiguous')
+    focal, tol = _views_ready(what, [d, p] if m is None else [d, p, m], focal=focal, tol=tol)
     if m is not None:
         d = torch.where(m, d, torch.zeros((), device=d.device, dtype=_F32)).contiguous()
     agree = torch.empty((V, H, W), device=d.device, dtype=_I32)

@@ -1,16 +1,12 @@
 """The definition of cross-view depth consistency, restated in numpy: what csrc/depth_consistency.hip computes, in fp64 on the
-fp32 inputs, with the expressions and the association of tests/warp_numpy.py::warp (dtype=np.float64).
+fp32 inputs.  The camera (unproject, project, in_image, lower_footprint, lower_blend) is tests/camera_numpy.py's with T = fp64.
 
 A target is a pixel (y, x) of view n with a finite disparity d > 0:
-    t = 1 / d,  dx = (x - W * .5) / f,  dy = -((y - H * .5) / f),  p_c = (t dx, t dy, -t)
-    p_w[c] = ((p_c[0] R[c][0] + p_c[1] R[c][1]) + p_c[2] R[c][2]) + o[c]
+    p_w = unproject(pose_n, x, y, t = 1 / d)
   for every view s != n:
-    dl = p_w - o_s,  q[j] = (R_s[0][j] dl[0] + R_s[1][j] dl[1]) + R_s[2][j] dl[2],  t_s = -q[2]
-    u = (f q[0]) / t_s + W * .5,  v = -((f q[1]) / t_s) + H * .5
-    in range: t_s > 0, 0 <= u <= W - 1, 0 <= v <= H - 1          (a NaN fails every comparison)
-    x0 = min(floor(u), W - 2), y0 = min(floor(v), H - 2), fx = u - x0, fy = v - y0
-    valid: all four taps of view s's disparity finite and > 0
-    d_s = the bilinear value (each row first, then the two rows),  resid = t_s d_s - 1
+    (u, v, t_s) = project(pose_s, p_w);  in range: in_image(t_s, u, v)
+    valid: all four taps of view s's disparity on the lower_footprint of (u, v) finite and > 0
+    d_s = lower_blend of the taps,  resid = t_s d_s - 1
     agree[n, y, x]    counts the views in range, valid, with |resid| <= tol
     violated[n, y, x] counts the views in range, valid, with resid < -tol     (s sees a farther surface through the point)
     resid > tol: occluded in s, nothing counted
@@ -18,7 +14,9 @@ A pixel that is not a target gets 0 / 0.  focal and tol enter as the fp32 values
 """
 import numpy as np
 
+import camera_numpy as C
 import warp_numpy as wn
+from camera_numpy import project_points as project      # noqa: F401  (the tests' fp64 bookkeeping helper)
 
 
 def consistency(disp, poses, focal, tol=0.05, masks=None):
@@ -34,34 +32,21 @@ def consistency(disp, poses, focal, tol=0.05, masks=None):
         usable = np.isfinite(d32) & (d32 > 0)
     d = d32.astype(T)
     f, tol = T(np.float32(focal)), T(np.float32(tol))
-    one, half = T(1), T(.5)
+    one = T(1)
     agree, violated = np.zeros((V, H, W), np.int32), np.zeros((V, H, W), np.int32)
     for n in range(V):
         ys, xs = np.nonzero(usable[n])
-        t = one / d[n, ys, xs]
-        dx = (xs.astype(T) - T(W) * half) / f
-        dy = -((ys.astype(T) - T(H) * half) / f)
-        pc = (t * dx, t * dy, -t)
-        R, o = pose[n, :, :3], pose[n, :, 3]
-        pw = [((pc[0] * R[c, 0] + pc[1] * R[c, 1]) + pc[2] * R[c, 2]) + o[c] for c in range(3)]
+        pw = C.unproject(T, pose[n], H, W, f, xs, ys, one / d[n, ys, xs])
         na, nv = np.zeros(len(ys), np.int32), np.zeros(len(ys), np.int32)
         for s in range(V):
             if s == n:
                 continue
-            Rs, os_ = pose[s, :, :3], pose[s, :, 3]
-            dl = [pw[c] - os_[c] for c in range(3)]
-            q = [(Rs[0, j] * dl[0] + Rs[1, j] * dl[1]) + Rs[2, j] * dl[2] for j in range(3)]
-            ts = -q[2]
+            u, v, ts = C.project(T, pose[s], f, H, W, pw)
             with np.errstate(all='ignore'):
-                u = (f * q[0]) / ts + T(W) * half
-                v = -((f * q[1]) / ts) + T(H) * half
-                inr = (ts > 0) & (u >= 0) & (u <= W - 1) & (v >= 0) & (v <= H - 1)
-                uc, vc = np.where(inr, u, 0), np.where(inr, v, 0)
-                x0 = np.minimum(np.floor(uc), W - 2).astype(np.int64)
-                y0 = np.minimum(np.floor(vc), H - 2).astype(np.int64)
+                inr = C.in_image(ts, u, v, H, W)
+                x0, y0, fx, fy = C.lower_footprint(u, v, H, W)
                 valid = usable[s][y0, x0] & usable[s][y0, x0 + 1] & usable[s][y0 + 1, x0] & usable[s][y0 + 1, x0 + 1]
-                fx, fy = u - x0.astype(T), v - y0.astype(T)
-                ds = wn._bilinear(d[s], y0, x0, fy, fx, one)
+                ds = C.lower_blend(d[s], y0, x0, fy, fx)
                 res = ts * ds - one
                 ok = inr & valid
                 na += ok & (np.abs(res) <= tol)
@@ -109,11 +94,3 @@ def homography_case3():
     nrm, off = (0.15, -0.1, 1.0), -3.0
     disp = np.stack([wn.plane_disparity(p, H, W, f, nrm, off).astype(np.float32) for p in poses])
     return dict(H=H, W=W, focal=f, poses=poses, disp=disp)
-
-
-def project(points, c2w, focal, H, W):
-    """fp64 (t_s, u, v) of world points [..., 3] in camera c2w: for the tests' own bookkeeping, not part of the definition."""
-    c2w = np.asarray(c2w, np.float64)
-    q = (points - c2w[:, 3]) @ c2w[:, :3]
-    ts = -q[..., 2]
-    return ts, focal * q[..., 0] / ts + W * .5, -(focal * q[..., 1] / ts) + H * .5

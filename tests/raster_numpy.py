@@ -1,12 +1,10 @@
 """numpy restatement of the mesh rasteriser (csrc/raster.hip; ops.mesh_rasterize), written from the definition alone -- the role
 tests/mesh_ops_numpy.py has for the mesh clean-up.  Everything is fp64 and integers, so the kernels must agree BIT FOR BIT.
 
-Conventions (those of csrc/tsdf.hip and csrc/warp.hip): c2w [3, 4] row-major = [R | o], the camera looks down -z, no half-pixel
-offset (pixel (x, y) is the sample point u = x, w = y), disparity = 1 / planar depth, faces counter-clockwise seen from outside.
+The camera (project and its conventions) is tests/camera_numpy.py's with T = fp64; faces are counter-clockwise seen from outside.
 
-Per view, per vertex p (fp32 widened to fp64, this operation order):
-    dl = p - o;  q[j] = (R[0][j] dl[0] + R[1][j] dl[1]) + R[2][j] dl[2];  z = -q[2]
-    u = (f q[0]) / z + W/2;  w = -((f q[1]) / z) + H/2;  d = 1 / z
+Per view, per vertex p (fp32 widened to fp64):
+    (u, w, z) = project(pose, p);  d = 1 / z
     X = rint(256 u), Y = rint(256 w)                  8 sub-pixel bits, ties to even, integers from here on
 Per face: dropped whole for the view unless every vertex has z >= near and |256 u|, |256 w| <= 2^22 (compared in fp64 before
 the conversion; a NaN fails).  THERE IS NO NEAR-PLANE CLIPPING: a face that straddles z = near vanishes.  A2 = (X1 - X0)(Y2 - Y0)
@@ -22,6 +20,8 @@ clamped to 0..255 of c = ((b0 c0 + b1 c1) + b2 c2) / ((b0 + b1) + b2), b_k = E_k
 """
 import numpy as np
 
+import camera_numpy as C
+
 F32, F64, I64 = np.float32, np.float64, np.int64
 SUB = 256
 BAND = 2.0 ** 22
@@ -31,14 +31,8 @@ CULLS = ('none', 'back')
 def project(verts, c2w, H, W, focal, near):
     """(X, Y int64 [Nv], d fp64 [Nv], ok bool [Nv]) of one view; X = Y = 0 where not ok."""
     p = np.asarray(verts, F32).astype(F64).reshape(-1, 3)
-    P = np.asarray(c2w, F32).astype(F64).reshape(3, 4)
-    f = F64(focal)
+    u, w, z = C.project(F64, np.asarray(c2w, F32).astype(F64).reshape(3, 4), F64(focal), H, W, p.T)
     with np.errstate(all='ignore'):
-        dl = [p[:, a] - P[a, 3] for a in range(3)]
-        q = [(P[0, j] * dl[0] + P[1, j] * dl[1]) + P[2, j] * dl[2] for j in range(3)]
-        z = -q[2]
-        u = (f * q[0]) / z + F64(W) * 0.5
-        w = -((f * q[1]) / z) + F64(H) * 0.5
         d = 1.0 / z
         su, sw = 256.0 * u, 256.0 * w
         ok = (z >= F64(near)) & (np.abs(su) <= BAND) & (np.abs(sw) <= BAND)

@@ -31,6 +31,7 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import camera_numpy as C                                 # noqa: E402
 import raster_numpy as N                                 # noqa: E402
 
 F32, F64, I64 = np.float32, np.float64, np.int64
@@ -119,15 +120,7 @@ def atlas_points(verts, faces, n):
 
 def project_point(p, c2w, H, W, focal):
     """(u, w, z) fp64 [N] of fp64 points p [N, 3]: the projection of raster_numpy.project, nothing tested."""
-    P = np.asarray(c2w, F32).astype(F64).reshape(3, 4)
-    f = F64(focal)
-    with np.errstate(all='ignore'):
-        dl = [p[:, a] - P[a, 3] for a in range(3)]
-        q = [(P[0, j] * dl[0] + P[1, j] * dl[1]) + P[2, j] * dl[2] for j in range(3)]
-        z = -q[2]
-        u = (f * q[0]) / z + F64(W) * 0.5
-        w = -((f * q[1]) / z) + F64(H) * 0.5
-    return u, w, z
+    return C.project(F64, np.asarray(c2w, F32).astype(F64).reshape(3, 4), F64(focal), H, W, p.T)
 
 
 def _bilinear(c00, c10, c01, c11, fx, fy):

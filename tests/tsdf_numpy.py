@@ -2,17 +2,15 @@
 precision `dtype` (np.float64: the yardstick; np.float32: the kernel's own arithmetic, operation for operation), and marching
 cubes restricted to observed cells (mvip_mcubes_count_valid), built on tests/mc_numpy.py.
 
-Conventions (csrc/warp.hip, csrc/mcubes.hip): no half-pixel offset, c2w [3, 4] row-major = [R | o], a camera-space point is
-t * ((x - W/2) / f, -(y - H/2) / f, -1), disparity = 1 / planar depth; lattice point (i, j, k) sits at x0 + i * hx, ...,
-hx = (x1 - x0) / (nx - 1); tsdf / count [nx, ny, nz], z fastest.
+The camera (project, in_image and their conventions) is tests/camera_numpy.py's; the lattice is csrc/mcubes.hip's: point
+(i, j, k) sits at x0 + i * hx, ..., hx = (x1 - x0) / (nx - 1); tsdf / count [nx, ny, nz], z fastest.
 
 Per lattice point p, the views in ascending order:
     acc = 0, cnt = 0
     for v = 0 .. V-1:
-        dl = p - o_v,   q[j] = (R_v[0][j] dl[0] + R_v[1][j] dl[1]) + R_v[2][j] dl[2],   z = -q[2]
-        u = (f q[0]) / z + W * .5,   w = -((f q[1]) / z) + H * .5
+        (u, w, z) = project(pose_v, p)
         xi = floor(u + .5),  yi = floor(w + .5)                    the nearest pixel
-        skip unless z > 0, 0 <= xi <= W - 1, 0 <= yi <= H - 1      (a NaN fails every comparison)
+        skip unless in_image(z, xi, yi)                            (a NaN fails every comparison)
         skip if a mask is given and mask[v][yi][xi] == 0
         d = disp[v][yi][xi];  skip unless d finite and > 0
         sdf = 1 / d - z;  skip if sdf < -trunc
@@ -21,6 +19,7 @@ Per lattice point p, the views in ascending order:
 """
 import numpy as np
 
+import camera_numpy as C
 import mc_numpy
 from warp_numpy import box_scene_disparity, plane_disparity, pose
 
@@ -61,16 +60,11 @@ def fuse(disp, poses, focal, bound_min, bound_max, resolution, trunc, masks=None
     acc, cnt = np.zeros(px.shape[0], T), np.zeros(px.shape[0], np.int32)
     excluded = np.zeros(px.shape[0], bool)
     for v in range(V):
-        R, o = poses[v, :, :3], poses[v, :, 3]
-        dl = [px - o[0], py - o[1], pz - o[2]]
-        q = [(R[0, j] * dl[0] + R[1, j] * dl[1]) + R[2, j] * dl[2] for j in range(3)]
-        z = -q[2]
+        u, w, z = C.project(T, poses[v], f, H, W, (px, py, pz))
         with np.errstate(all='ignore'):
-            u = (f * q[0]) / z + T(W) * half
-            w = -((f * q[1]) / z) + T(H) * half
             su, sw = u + half, w + half
             fx, fy = np.floor(su), np.floor(sw)
-            inr = (z > 0) & (fx >= 0) & (fx <= W - 1) & (fy >= 0) & (fy <= H - 1)
+            inr = C.in_image(z, fx, fy, H, W)
             xi = np.where(inr, fx, 0).astype(np.int64)
             yi = np.where(inr, fy, 0).astype(np.int64)
             d = disp[v, yi, xi]
@@ -256,11 +250,8 @@ def hit_pixel(case, view):
     T = np.float64
     xs, ys, zs = lattice(case['bound_min'], case['bound_max'], case['resolution'], T)
     p = np.stack(np.meshgrid(xs, ys, zs, indexing='ij'), -1).reshape(-1, 3)[c.reshape(-1) > 0]
-    P = case['poses'][view].astype(T)
-    q = (p - P[:, 3]) @ P[:, :3]
-    f = T(np.float32(case['focal']))
-    xi = np.floor(f * q[:, 0] / -q[:, 2] + W * .5 + .5).astype(np.int64)
-    yi = np.floor(-(f * q[:, 1] / -q[:, 2]) + H * .5 + .5).astype(np.int64)
+    _, u, w = C.project_points(p, case['poses'][view], T(np.float32(case['focal'])), H, W)
+    xi, yi = np.floor(u + .5).astype(np.int64), np.floor(w + .5).astype(np.int64)
     hits = np.bincount(yi * W + xi, minlength=H * W)
     return int(hits.argmax() // W), int(hits.argmax() % W)
 

@@ -1,25 +1,22 @@
 """The definition of reference-view propagation (backward depth warping), restated in numpy: what csrc/warp.hip computes,
 in the precision `dtype` (np.float64: the yardstick; np.float32: the kernel's own arithmetic, operation for operation).
 
-Conventions (get_rays', csrc/rays.hip): no half-pixel offset, c2w [3, 4] row-major = [R | o]; the ray parameter is the planar
-depth t, a camera-space point is t * ((x - W/2) / f, -(y - H/2) / f, -1); disparity = 1 / t.
+The camera (unproject, project, in_image, lower_footprint, lower_blend and their conventions) is tests/camera_numpy.py's.
 
 Per target n and pixel (y, x) with tgt_mask set and a finite tgt_disp > 0:
-    t   = 1 / disp
-    dx  = (x - W * .5) / f,  dy = -((y - H * .5) / f),  p_c = (t * dx, t * dy, -t)
-    p_w[c] = ((p_c[0] R[c][0] + p_c[1] R[c][1]) + p_c[2] R[c][2]) + o[c]
+    p_w = unproject(pose_n, x, y, t = 1 / disp)
   for k = 0 .. S-1, s = order[n][k] (skipped unless 0 <= s < S), until a source is taken:
-    dl  = p_w - o_s,   q[j] = (R_s[0][j] dl[0] + R_s[1][j] dl[1]) + R_s[2][j] dl[2],   t_s = -q[2]
-    u   = (f q[0]) / t_s + W * .5,   v = -((f q[1]) / t_s) + H * .5
-    in range:  t_s > 0,  0 <= u <= W - 1,  0 <= v <= H - 1        (a NaN fails every comparison)
-    x0  = min(floor(u), W - 2),  y0 = min(floor(v), H - 2),  fx = u - x0,  fy = v - y0,  gx = 1 - fx,  gy = 1 - fy
-    a   = (a[y0][x0] gx + a[y0][x0+1] fx) gy + (a[y0+1][x0] gx + a[y0+1][x0+1] fx) fy      each row first, then the two rows;
-          the same weights for the source's disparity d_s and its three colour channels
+    (u, v, t_s) = project(pose_s, p_w);  in range: in_image(t_s, u, v)
+    a   = lower_blend on the lower_footprint of (u, v): the same weights for the source's disparity d_s and its three colour
+          channels
     resid = t_s d_s - 1
     taken iff in range, d_s finite and > 0, |resid| <= tol, the three colours finite
 Outputs rgb [N, H, W, 3], index [N, H, W] int32 (the source, or -1), resid [N, H, W]; 0 / -1 / 0 wherever no source is taken.
 """
 import numpy as np
+
+import camera_numpy as C
+from camera_numpy import pose                        # noqa: F401  (the cases' poses; imported from here by the tests)
 
 M_T = 2.0 ** -16           # margins of the exclusion rule (warp(..., details=True))
 M_R = 2.0 ** -16
@@ -27,15 +24,6 @@ M_R = 2.0 ** -16
 
 def default_order(N, S):
     return np.tile(np.arange(S, dtype=np.int32), (N, 1)).reshape(N, S)
-
-
-def _bilinear(a, y0, x0, fy, fx, one):
-    gx, gy = one - fx, one - fy
-    if a.ndim == 3:
-        fx, fy, gx, gy = fx[:, None], fy[:, None], gx[:, None], gy[:, None]
-    top = a[y0, x0] * gx + a[y0, x0 + 1] * fx
-    bot = a[y0 + 1, x0] * gx + a[y0 + 1, x0 + 1] * fx
-    return top * gy + bot * fy
 
 
 def warp(tgt_disp, tgt_pose, tgt_mask, src_rgb, src_disp, src_pose, focal, order=None, tol=0.05, dtype=np.float64, details=False):
@@ -54,19 +42,14 @@ def warp(tgt_disp, tgt_pose, tgt_mask, src_rgb, src_disp, src_pose, focal, order
     assert tgt_pose.shape == (N, 3, 4) and tgt_mask.shape == (N, H, W) and order.shape == (N, S) and H >= 2 and W >= 2
     assert src_rgb.shape == (S, H, W, 3) and src_disp.shape == (S, H, W) and src_pose.shape == (S, 3, 4)
     f, tol = T(np.float32(focal)), T(np.float32(tol))
-    one, half, m_uv = T(1), T(.5), 2.0 ** -18 * max(H, W)
+    one, m_uv = T(1), 2.0 ** -18 * max(H, W)
     rgb, index, resid = np.zeros((N, H, W, 3), T), np.full((N, H, W), -1, np.int32), np.zeros((N, H, W), T)
     excluded = np.zeros((N, H, W), bool)
     for n in range(N):
         d = tgt_disp[n]
         with np.errstate(invalid='ignore'):
             ys, xs = np.nonzero(tgt_mask[n] & np.isfinite(d) & (d > 0))
-        t = one / d[ys, xs]
-        dx = (xs.astype(T) - T(W) * half) / f
-        dy = -((ys.astype(T) - T(H) * half) / f)
-        pc = (t * dx, t * dy, -t)
-        R, o = tgt_pose[n, :, :3], tgt_pose[n, :, 3]
-        pw = [((pc[0] * R[c, 0] + pc[1] * R[c, 1]) + pc[2] * R[c, 2]) + o[c] for c in range(3)]
+        pw = C.unproject(T, tgt_pose[n], H, W, f, xs, ys, one / d[ys, xs])
         got_i, got_c, got_e = np.full(len(ys), -1, np.int32), np.zeros((len(ys), 3), T), np.zeros(len(ys), T)
         marginal = np.zeros(len(ys), bool)
         for k in range(S):
@@ -74,21 +57,12 @@ def warp(tgt_disp, tgt_pose, tgt_mask, src_rgb, src_disp, src_pose, focal, order
             sel = np.nonzero(got_i < 0)[0]
             if not 0 <= s < S or sel.size == 0:
                 continue
-            Rs, os_ = src_pose[s, :, :3], src_pose[s, :, 3]
-            dl = [pw[c][sel] - os_[c] for c in range(3)]
-            q = [(Rs[0, j] * dl[0] + Rs[1, j] * dl[1]) + Rs[2, j] * dl[2] for j in range(3)]
-            ts = -q[2]
+            u, v, ts = C.project(T, src_pose[s], f, H, W, [pw[c][sel] for c in range(3)])
             with np.errstate(all='ignore'):
-                u = (f * q[0]) / ts + T(W) * half
-                v = -((f * q[1]) / ts) + T(H) * half
-                inr = (ts > 0) & (u >= 0) & (u <= W - 1) & (v >= 0) & (v <= H - 1)
-                # out of range: never taken; the taps are clamped into the image so that the details below can look at them
-                uc, vc = np.where(np.isfinite(u), u, 0), np.where(np.isfinite(v), v, 0)
-                x0 = np.clip(np.floor(uc), 0, W - 2).astype(np.int64)
-                y0 = np.clip(np.floor(vc), 0, H - 2).astype(np.int64)
-                fx, fy = u - x0.astype(T), v - y0.astype(T)
-                ds = _bilinear(src_disp[s], y0, x0, fy, fx, one)
-                col = _bilinear(src_rgb[s], y0, x0, fy, fx, one)
+                inr = C.in_image(ts, u, v, H, W)
+                x0, y0, fx, fy = C.lower_footprint(u, v, H, W)         # out of range: never taken, but the details look at the taps
+                ds = C.lower_blend(src_disp[s], y0, x0, fy, fx)
+                col = C.lower_blend(src_rgb[s], y0, x0, fy, fx)
                 res = ts * ds - one
                 ok = inr & np.isfinite(ds) & (ds > 0) & (np.abs(res) <= tol) & np.isfinite(col).all(-1)
                 if details:
@@ -119,21 +93,11 @@ def yardstick(*args, **kw):
     return out
 
 
-def pose(angles=(0., 0., 0.), origin=(0., 0., 0.)):
-    """c2w [3, 4] fp32: rotations about x, y, z (radians) composed as Rz Ry Rx, and the camera centre."""
-    ax, ay, az = angles
-    cx, sx, cy, sy, cz, sz = np.cos(ax), np.sin(ax), np.cos(ay), np.sin(ay), np.cos(az), np.sin(az)
-    Rx = np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]])
-    Ry = np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])
-    Rz = np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]])
-    return np.concatenate([Rz @ Ry @ Rx, np.asarray(origin, np.float64)[:, None]], 1).astype(np.float32)
-
-
 def pixel_rays(c2w, H, W, focal):
     """fp64 origins o [3] and directions d [H, W, 3] of the pixel rays in world space (planar depth: point = o + t d)."""
     c2w = np.asarray(c2w, np.float64)
     y, x = np.mgrid[0:H, 0:W].astype(np.float64)
-    dirs = np.stack([(x - W * .5) / focal, -(y - H * .5) / focal, -np.ones_like(x)], -1)
+    dirs = np.stack([*C.pixel_dir(np.float64, x, y, H, W, focal), -np.ones_like(x)], -1)
     return c2w[:, 3], dirs @ c2w[:, :3].T
 
 
