@@ -1132,6 +1132,37 @@ int mvip_mesh_sample_faces(const float *verts, const int *faces, int64_t n_verts
                            int *face_of_sample, double *weights, int *flag, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Mesh ray casting: the first face each of N rays hits, occlusion, and per face the number of directions in which it sees
+ * nothing (beyond the reference, which has no mesh export: no entry point has a reference call site; csrc/mesh_raycast.hip,
+ * ops.mesh_cast_rays / mesh_occluded / mesh_face_openness, mesh.cast_rays / cast_views / face_openness / drop_interior).  The
+ * definition -- the watertight ray-triangle test in fp64 with its operation order, the tie rule, invalid rays -- is written out
+ * in csrc/mesh_raycast.hip and tests/mesh_raycast_numpy.py; the result does not depend on the grid.  The mesh and its face
+ * grid are the operands of mvip_mesh_distance_query (cell_offsets / cell_faces of mvip_mesh_distance_grid_fill for the same
+ * box and cells); bounds[6] (HOST) = the fp32 minimum[3] and maximum[3] of the vertices, or any box that holds every face.
+ * One launch each on the caller's stream (plus one that clears stats), one thread per ray / per face, no atomics outside the
+ * stats: bit-reproducible.  MVIP_EINVAL before any device call for: a count < 0, V, 3 F, 3 N, 4 F or the pair count > 2^31 - 1,
+ * F = 0 (V = 0), a bad box / cells, bounds NULL, not finite or with minimum > maximum, any_hit not 0 / 1, n_dirs outside
+ * 0..255, max_dist NaN or < 0, a NULL operand that a non-zero count makes necessary.  N = 0 is valid.
+ * mvip_mesh_raycast: origins / dirs [N,3] fp32; tmin / tmax [N] fp32 or NULL (then tmin_all / tmax_all for every ray); skip [N]
+ *   int32 or NULL (the face that never counts for the ray, -1: none).  face [N] (-1: a miss or an invalid ray), t [N] or NULL
+ *   (+inf: a miss, NaN: an invalid ray), bary [N,2] or NULL (the weights of the face's second and third vertex; NaN without a
+ *   hit).  any_hit = 1: the traversal stops at the first accepted hit, face is that face and t / bary are its.
+ *   stats: NULL, or three 64-bit words that are cleared and receive the number of ray-face tests, summed over the waves 64
+ *   times the tests of the wave's busiest lane, and the number of cells visited (a counting variant of the kernel).
+ * mvip_mesh_face_openness: directions [K,3] fp32 (DEVICE), counts [4,F] int32 = front_open, front_total, back_open,
+ *   back_total per face; the rays (centroid, d_k, 0, max_dist) with the face itself skipped, generated in the kernel.  A face
+ *   with an index outside [0, V) gets zeros.  stats as above. */
+int mvip_mesh_raycast(const float *origins, const float *dirs, const float *tmin, const float *tmax, float tmin_all,
+                      float tmax_all, const int *skip, int64_t n_rays, const float *verts, const int *faces, int64_t n_verts,
+                      int64_t n_faces, const float *box, const int *cells, const float *bounds, const int *cell_offsets,
+                      const int *cell_faces, int64_t n_pairs, int any_hit, int *face, float *t, float *bary, void *stats,
+                      void *stream);
+int mvip_mesh_face_openness(const float *verts, const int *faces, int64_t n_verts, int64_t n_faces, const float *box,
+                            const int *cells, const float *bounds, const int *cell_offsets, const int *cell_faces,
+                            int64_t n_pairs, const float *directions, int n_dirs, float max_dist, int *counts, void *stats,
+                            void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Quantile termination depth of a ray, and agreement / free-space violations of depth maps across views (beyond the
  * reference, which renders only the expected depth and never compares views: no entry point has a reference call site;
  * csrc/ray_depth.hip, csrc/depth_consistency.hip, ops.ray_quantile_depth / depth_consistency, prepare.consistency_mask).

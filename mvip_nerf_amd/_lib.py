@@ -235,6 +235,10 @@ _SIGNATURES = {
     'mvip_mesh_distance_query': (_int, [_c_f, _i64, _c_f, _c_f, _i64, _i64, ctypes.POINTER(_flt), ctypes.POINTER(_int), _c_f, _c_f,
                                         _i64, _c_f, _c_f, _c_f, _c_f, _c_f]),
     'mvip_mesh_sample_faces': (_int, [_c_f, _c_f, _i64, _i64, _int, _c_f, _c_f, _c_f, _c_f, _c_f]),
+    'mvip_mesh_raycast': (_int, [_c_f, _c_f, _c_f, _c_f, _flt, _flt, _c_f, _i64, _c_f, _c_f, _i64, _i64, ctypes.POINTER(_flt),
+                                 ctypes.POINTER(_int), ctypes.POINTER(_flt), _c_f, _c_f, _i64, _int, _c_f, _c_f, _c_f, _c_f, _c_f]),
+    'mvip_mesh_face_openness': (_int, [_c_f, _c_f, _i64, _i64, ctypes.POINTER(_flt), ctypes.POINTER(_int), ctypes.POINTER(_flt),
+                                       _c_f, _c_f, _i64, _c_f, _int, _flt, _c_f, _c_f, _c_f]),
     'mvip_ray_quantile_depth': (_int, [_c_f, _c_f, _i64, _int, ctypes.POINTER(_flt), _int, _c_f, _c_f]),
     'mvip_depth_consistency': (_int, [_c_f, _c_f, _int, _int, _int, _flt, _flt, _c_f, _c_f, _c_f]),
 }

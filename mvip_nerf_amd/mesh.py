@@ -15,6 +15,9 @@ bake_texture() / colors_from_views() / render_textured() / save_obj() take the c
 the textured mesh rendered back into a camera, and OBJ + MTL + PNG export.
 load_ply() reads back what save_ply() wrote, bit for bit; how far two meshes lie apart is evaluate.mesh_distance_metrics
 (csrc/mesh_distance.hip).
+cast_rays() / cast_views() / face_openness() / drop_interior() ask what a ray hits (csrc/mesh_raycast.hip): the first face along
+render_rays' own ray rows, frames without the rasteriser's near-plane drop, and the faces of interior shells that see nothing
+but mesh.
 
 Conventions (shared with csrc/mcubes.hip and the test restatement tests/mc_numpy.py): grid [nx, ny, nz], z fastest; point
 (i, j, k) sits at bmin + (i, j, k) * (bmax - bmin) / (n - 1), in fp32 arithmetic; a corner is inside iff sigma >= threshold
@@ -612,6 +615,92 @@ def keep_faces(mesh, keep):
     new = (torch.cumsum(used, 0) - 1).to(torch.int32)
     pick = lambda a: None if a is None else a[used].contiguous()
     return Mesh(pick(mesh.verts), new[faces.to(torch.int64)].contiguous(), pick(mesh.normals), pick(mesh.colors))
+
+
+def cast_rays(mesh, rows, grid=None):
+    """(face [B] int32, depth [B] fp32, disparity [B] fp32) of run.render_rays' own ray rows [B, 8 | 11] (origin, direction,
+    near, far, ...) cast against `mesh` (ops.mesh_cast_rays, csrc/mesh_raycast.hip): the first face hit between near and far,
+    -1 for none; depth = the ray parameter of the hit, which for the rows of get_rays (camera z = -1) is the planar depth, +inf
+    for none; disparity = 1 / depth and 0 for none -- the conventions of render_views and prepare.render_disparities."""
+    rows = torch.as_tensor(rows)
+    if rows.dim() != 2 or rows.shape[1] not in (8, 11) or rows.dtype != torch.float32:
+        raise ValueError(f'cast_rays: rows must be fp32 [B, 8] or [B, 11], got {rows.dtype} {tuple(rows.shape)}')
+    rows = rows.detach().to(mesh.verts.device)
+    face, depth = ops.mesh_cast_rays(rows[:, 0:3].contiguous(), rows[:, 3:6].contiguous(), mesh.verts, mesh.faces,
+                                     tmin=rows[:, 6].contiguous(), tmax=rows[:, 7].contiguous(), grid=grid)
+    return face, depth, torch.where(face >= 0, (1.0 / depth.double()).float(), torch.zeros_like(depth))
+
+
+def cast_views(mesh, hwf, poses, near, far, colors=True):
+    """(disp [V, H, W] fp32, face [V, H, W] int32, rgb [V, H, W, 3] uint8 or None) of `mesh` ray cast into the cameras poses
+    [V, 3, >=4]: render_views' outputs in render_views' conventions, from one ray per pixel centre (ops.get_rays) instead of the
+    rasteriser.  A face that crosses the near plane is still seen beyond it, where render_views drops it whole.  rgb is the
+    barycentric mean of the hit face's vertex colours, rounded to the nearest byte (None with colors=False or a mesh without
+    colours).  The two renderers agree except along silhouettes and shared edges: the rasteriser snaps vertices to 8 sub-pixel
+    bits and fills by the top-left rule, the ray cast does neither."""
+    H, W, focal = int(hwf[0]), int(hwf[1]), float(hwf[2])
+    dev = mesh.verts.device
+    poses = _view_poses(poses, dev)
+    V = int(poses.shape[0])
+    want_rgb = colors and mesh.colors is not None
+    if V == 0:
+        return (torch.zeros((0, H, W), device=dev), torch.zeros((0, H, W), device=dev, dtype=torch.int32),
+                torch.zeros((0, H, W, 3), device=dev, dtype=torch.uint8) if want_rgb else None)
+    rays = [ops.get_rays(H, W, focal, p) for p in poses]
+    o = torch.stack([r[0] for r in rays]).reshape(-1, 3)
+    d = torch.stack([r[1] for r in rays]).reshape(-1, 3)
+    out = ops.mesh_cast_rays(o, d, mesh.verts, mesh.faces, tmin=float(near), tmax=float(far), return_bary=want_rgb)
+    face, depth = out[0], out[1]
+    hit = face >= 0
+    disp = torch.where(hit, (1.0 / depth.double()).float(), torch.zeros_like(depth)).reshape(V, H, W)
+    rgb = None
+    if want_rgb:
+        bary = torch.nan_to_num(out[2])
+        corner = mesh.faces[face.clamp(min=0).to(torch.int64)].to(torch.int64)             # [B, 3]
+        c = mesh.colors[corner].to(torch.float32)                                        # [B, 3 corners, 3 channels]
+        w = torch.stack([1.0 - bary[:, 0] - bary[:, 1], bary[:, 0], bary[:, 1]], 1)
+        mixed = (c * w[:, :, None]).sum(1)
+        rgb = torch.where(hit[:, None], (mixed + 0.5).floor().clamp(0, 255), torch.zeros_like(mixed)).to(torch.uint8).reshape(V, H, W, 3)
+    return disp, face.reshape(V, H, W), rgb
+
+
+def fibonacci_directions(count):
+    """[count, 3] fp32 numpy: the spherical Fibonacci set z_i = 1 - (2 i + 1) / count, phi_i = pi (1 + sqrt 5) (i + 1/2),
+    (sqrt(1 - z^2) cos phi, sqrt(1 - z^2) sin phi, z), computed in fp64 and rounded once.  Nothing is random."""
+    if isinstance(count, bool) or int(count) != count or not 1 <= int(count) <= ops.MESH_OPENNESS_MAX_DIRECTIONS:
+        raise ValueError(f'fibonacci_directions: count must be an integer in 1..{ops.MESH_OPENNESS_MAX_DIRECTIONS}, got {count!r}')
+    i = np.arange(int(count), dtype=np.float64)
+    z = 1.0 - (2.0 * i + 1.0) / int(count)
+    phi = np.pi * (1.0 + np.sqrt(5.0)) * (i + 0.5)
+    r = np.sqrt(1.0 - z * z)
+    return np.stack([r * np.cos(phi), r * np.sin(phi), z], 1).astype(np.float32)
+
+
+def _openness_args(mesh, directions, max_dist):
+    if not torch.is_tensor(directions):
+        directions = fibonacci_directions(directions) if np.isscalar(directions) else np.asarray(directions, np.float32)
+        directions = torch.from_numpy(np.ascontiguousarray(directions))
+    directions = directions.to(device=mesh.verts.device, dtype=torch.float32).contiguous()
+    return directions, float('inf') if max_dist is None else float(max_dist)
+
+
+def face_openness(mesh, directions=32, max_dist=None):
+    """(front_open, front_total, back_open, back_total), int32 [F] each (ops.mesh_face_openness, csrc/mesh_raycast.hip): of the
+    directions on a face's front side (N . d > 0, N the face normal of counter-clockwise faces) and on its back side, how many
+    see nothing of the mesh within max_dist (None: no limit) from the face's centroid.  directions: a count (the spherical
+    Fibonacci set of that size) or [K, 3] directions, K <= 255.  An exterior face of a closed surface has every front direction
+    open; a face of an interior shell has none on either side."""
+    d, far = _openness_args(mesh, directions, max_dist)
+    return ops.mesh_face_openness(mesh.verts, mesh.faces, d, max_dist=far)
+
+
+def drop_interior(mesh, directions=32, two_sided=True, max_dist=None):
+    """The mesh without the faces that see nothing but mesh (face_openness, keep_faces): a face stays iff at least one direction
+    is open on either side (two_sided=True: right for level sets whose orientation is not trusted, and for open sheets) or on
+    its front side (two_sided=False: also drops the inner wall of a thick shell).  Unlike keeping the faces some camera saw
+    (visible_faces), exterior surface that no camera happened to see stays."""
+    fo, _, bo, _ = face_openness(mesh, directions, max_dist)
+    return keep_faces(mesh, (fo + bo > 0) if two_sided else (fo > 0))
 
 
 Texture = collections.namedtuple('Texture', ['image', 'uv', 'seen', 'texels'])

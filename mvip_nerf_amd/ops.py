@@ -2788,12 +2788,14 @@ MESH_SAMPLE_MAX_SUBDIVISION = 1024
 class FaceGrid:
     """The face lists of one mesh on a uniform grid (ops.mesh_face_grid): reusable for any number of mesh_closest_point calls
     on the same verts / faces tensors.  box = (bmin[3], inv[3]) fp32, cells (cx, cy, cz), cell_offsets [n_cells + 1] int32,
-    cell_faces [n_pairs] int32 (each cell's faces ascending), n_pairs."""
+    cell_faces [n_pairs] int32 (each cell's faces ascending), n_pairs; bounds = the fp32 (minimum[3], maximum[3]) of the vertices
+    as a host array [6] (what the ray casts of csrc/mesh_raycast.hip cut their rays to)."""
 
-    def __init__(self, verts, faces, box, cells, cell_offsets, cell_faces):
+    def __init__(self, verts, faces, box, cells, cell_offsets, cell_faces, bounds=None):
         self.verts, self.faces, self.box, self.cells = verts, faces, box, cells
         self.cell_offsets, self.cell_faces = cell_offsets, cell_faces
         self.n_pairs = int(cell_faces.shape[0])
+        self.bounds = bounds
         self._key = self._key_of(verts, faces)
 
     @staticmethod
@@ -2883,7 +2885,7 @@ def mesh_face_grid(verts, faces, cells=None):
     scratch = torch.empty(words, device=dev, dtype=_I32)
     call('mvip_mesh_distance_grid_fill', ptr(v), ptr(f, _I32), V, F, cbox, ccells, ptr(face_off, torch.int64), P, ptr(cell_off, _I32),
          ptr(cell_faces, _I32), ptr(scratch, _I32), st)
-    return FaceGrid(v, f, box, counts, cell_off, cell_faces)
+    return FaceGrid(v, f, box, counts, cell_off, cell_faces, bounds=lohi.reshape(6).astype(np.float32))
 
 
 def mesh_closest_point(points, verts, faces, grid=None, return_stats=False):
@@ -2961,6 +2963,152 @@ def mesh_sample_faces(verts, faces, k):
     if int(flag.cpu()):
         raise ValueError(f'{what}: a face index lies outside [0, {V})')
     return pts, fos, w
+
+
+# mesh ray casting: first hit, occlusion, face openness on the face grid (beyond the reference, csrc/mesh_raycast.hip) ---------------
+# The definition is csrc/mesh_raycast.hip's and tests/mesh_raycast_numpy.py's.  There is no CPU path.
+
+MESH_OPENNESS_MAX_DIRECTIONS = 255
+
+
+def _ray_operand(what, name, t, width, dev, dtype=None):
+    dtype = _F32 if dtype is None else dtype
+    if not torch.is_tensor(t):
+        raise ValueError(f'{what}: {name} must be a tensor on the GPU, got {type(t).__name__}')
+    if t.dtype != dtype:
+        raise ValueError(f'{what}: {name} must be {dtype}, got {t.dtype}')
+    if (t.dim() != 2 or t.shape[1] != width) if width else t.dim() != 1:
+        raise ValueError(f'{what}: {name} must be {"[N, %d]" % width if width else "[N]"}, got {tuple(t.shape)}')
+    t = t.detach()
+    if not t.is_cuda:
+        raise ValueError(f'{what}: tensors on the GPU expected (the HIP path has no CPU path)')
+    if t.device != dev:
+        raise ValueError(f'{what}: tensors on one device expected, got {sorted({str(dev), str(t.device)})}')
+    if not t.is_contiguous():
+        raise ValueError(f'{what}: every operand must be contiguous')
+    return t
+
+
+def _ray_grid(what, v, f, grid):
+    """the FaceGrid of (v, f) with its vertex bounds, and the host arrays of the C ABI"""
+    import ctypes
+    import numpy as np
+    if grid is None:
+        grid = mesh_face_grid(v, f)
+    elif not isinstance(grid, FaceGrid) or not grid.matches(v, f):
+        raise ValueError(f'{what}: grid must be the mesh_face_grid of these verts and faces')
+    if grid.bounds is None:
+        grid.bounds = torch.stack([v.amin(0), v.amax(0)]).cpu().numpy().reshape(6).astype(np.float32)
+    cbox = (ctypes.c_float * 6)(*[float(x) for x in grid.box])
+    ccells = (ctypes.c_int * 3)(*grid.cells)
+    cbounds = (ctypes.c_float * 6)(*[float(x) for x in grid.bounds])
+    return grid, cbox, ccells, cbounds
+
+
+def _cast(what, any_hit, origins, dirs, verts, faces, tmin, tmax, skip, grid, return_bary, return_stats):
+    import math
+    v, f = _mesh_operands(what, verts, faces)
+    dev = v.device
+    o = _ray_operand(what, 'origins', origins, 3, dev)
+    d = _ray_operand(what, 'dirs', dirs, 3, dev)
+    N = int(o.shape[0])
+    if d.shape[0] != N:
+        raise ValueError(f'{what}: {N} origins but {int(d.shape[0])} dirs')
+    if 3 * N > 2 ** 31 - 1:
+        raise ValueError(f'{what}: {N} rays exceed int32 indices')
+    lims = []
+    for name, lim in (('tmin', tmin), ('tmax', tmax)):
+        if torch.is_tensor(lim):
+            lim = _ray_operand(what, name, lim, 0, dev)
+            if lim.shape[0] != N:
+                raise ValueError(f'{what}: {name} must be a number or [{N}], got {tuple(lim.shape)}')
+            lims.append((lim, 0.0))
+        else:
+            if isinstance(lim, bool) or not isinstance(lim, (int, float)) or math.isnan(float(lim)):
+                raise ValueError(f'{what}: {name} must be a number or a [N] tensor, got {lim!r}')
+            lims.append((None, float(lim)))
+    if skip is not None:
+        skip = _ray_operand(what, 'skip', skip, 0, dev, _I32)
+        if skip.shape[0] != N:
+            raise ValueError(f'{what}: skip must be [{N}], got {tuple(skip.shape)}')
+    if int(f.shape[0]) == 0 or int(v.shape[0]) == 0:
+        raise ValueError(f'{what}: a mesh of {int(f.shape[0])} faces and {int(v.shape[0])} vertices cannot be hit')
+    grid, cbox, ccells, cbounds = _ray_grid(what, v, f, grid)
+    V, F = int(v.shape[0]), int(f.shape[0])
+    face = torch.empty(N, device=dev, dtype=_I32)
+    t = None if any_hit else torch.empty(N, device=dev, dtype=_F32)
+    bary = torch.empty((N, 2), device=dev, dtype=_F32) if return_bary else None
+    stats = torch.empty(3, device=dev, dtype=torch.int64) if return_stats else None
+    none = ptr(None)
+    some = lambda x, dt=_F32: ptr(x, dt) if (x is not None and N) else none
+    call('mvip_mesh_raycast', some(o), some(d), some(lims[0][0]), some(lims[1][0]), lims[0][1], lims[1][1], some(skip, _I32), N,
+         ptr(v), ptr(f, _I32), V, F, cbox, ccells, cbounds, ptr(grid.cell_offsets, _I32),
+         ptr(grid.cell_faces, _I32) if grid.n_pairs else none, grid.n_pairs, 1 if any_hit else 0, some(face, _I32), some(t),
+         some(bary), ptr(stats, torch.int64) if return_stats else none, stream())
+    return face, t, bary, stats
+
+
+def mesh_cast_rays(origins, dirs, verts, faces, tmin=0., tmax=float('inf'), skip=None, grid=None, return_bary=False,
+                   return_stats=False):
+    """The first face of the mesh (verts [V, 3] fp32, faces [F, 3] int32) that each ray hits: (face [N] int32, t [N] fp32), all on
+    the GPU.  origins / dirs [N, 3] fp32; tmin / tmax numbers or [N] fp32 tensors; skip [N] int32 or None: one face per ray that
+    never counts (-1: none).  The definition (csrc/mesh_raycast.hip, tests/mesh_raycast_numpy.py): the watertight ray-triangle
+    test in fp64 on the widened inputs, no culling; the hit of smallest t in [tmin, tmax], the lowest face index among equals;
+    face -1 and t +inf for a miss; face -1 and t NaN for an invalid ray (a NaN or infinite origin or direction, a zero
+    direction, tmin not finite, tmax NaN or < tmin).  return_bary=True appends bary [N, 2] fp32, the weights of the face's
+    second and third vertex (NaN without a hit).  grid: a FaceGrid of mesh_face_grid for these very tensors (None: built
+    here); the result does not depend on it.  return_stats=True appends a [3] int64 device tensor (a counting variant of the
+    kernel): the ray-face tests, 64 times the tests of each wave's busiest lane summed over the waves, the cells visited.
+    N = 0 gives empty tensors.  ValueError for bad shapes or dtypes, CPU tensors, F = 0, a face index outside [0, V), a NaN or
+    infinite vertex, a grid of another mesh.  Detached."""
+    face, t, bary, stats = _cast('mesh_cast_rays', False, origins, dirs, verts, faces, tmin, tmax, skip, grid, return_bary,
+                                 return_stats)
+    return (face, t) + ((bary,) if return_bary else ()) + ((stats,) if return_stats else ())
+
+
+def mesh_occluded(origins, dirs, verts, faces, tmin=0., tmax=float('inf'), skip=None, grid=None, return_stats=False):
+    """[N] bool: does the ray hit any face -- face >= 0 of mesh_cast_rays, by a kernel that stops at the first accepted hit.  An
+    invalid ray is not occluded.  Arguments and errors as mesh_cast_rays; return_stats=True returns (occluded, stats)."""
+    face, _, _, stats = _cast('mesh_occluded', True, origins, dirs, verts, faces, tmin, tmax, skip, grid, False, return_stats)
+    return (face >= 0, stats) if return_stats else face >= 0
+
+
+def mesh_face_openness(verts, faces, directions, max_dist=float('inf'), grid=None, return_stats=False):
+    """Per face, in how many of the directions [K, 3] fp32 (K <= 255, finite, on the GPU) it sees nothing: (front_open,
+    front_total, back_open, back_total), each int32 [F].  The definition (csrc/mesh_raycast.hip): the ray from the fp64
+    centroid ((a + b) + c) / 3 along d_k over [0, max_dist] with the face itself skipped; d_k counts for the front side iff
+    N . d_k > 0, N = (b - a) x (c - a), for the back side iff < 0, for neither iff == 0; open iff the ray hits nothing.  The rays
+    are generated in the kernel, one thread per face.  F = 0 gives empty tensors.  return_stats as mesh_cast_rays.  ValueError
+    for bad shapes or dtypes, K > 255, a NaN or infinite direction, max_dist NaN or < 0, a grid of another mesh."""
+    import math
+    what = 'mesh_face_openness'
+    v, f = _mesh_operands(what, verts, faces)
+    dev = v.device
+    d = _ray_operand(what, 'directions', directions, 3, dev)
+    K = int(d.shape[0])
+    if K > MESH_OPENNESS_MAX_DIRECTIONS:
+        raise ValueError(f'{what}: at most {MESH_OPENNESS_MAX_DIRECTIONS} directions, got {K}')
+    if K and not bool(torch.isfinite(d).all()):
+        raise ValueError(f'{what}: a direction is NaN or infinite')
+    if isinstance(max_dist, bool) or not isinstance(max_dist, (int, float)) or math.isnan(float(max_dist)) or max_dist < 0:
+        raise ValueError(f'{what}: max_dist must be a number >= 0 (inf: no limit), got {max_dist!r}')
+    V, F = int(v.shape[0]), int(f.shape[0])
+    if F == 0:
+        if grid is not None:
+            raise ValueError(f'{what}: grid must be the mesh_face_grid of these verts and faces')
+        z = torch.zeros(0, device=dev, dtype=_I32)
+        return (z, z.clone(), z.clone(), z.clone()) + ((torch.zeros(3, device=dev, dtype=torch.int64),) if return_stats else ())
+    if 4 * F > 2 ** 31 - 1:
+        raise ValueError(f'{what}: {F} faces exceed int32 indices')
+    grid, cbox, ccells, cbounds = _ray_grid(what, v, f, grid)
+    counts = torch.empty((4, F), device=dev, dtype=_I32)
+    stats = torch.empty(3, device=dev, dtype=torch.int64) if return_stats else None
+    none = ptr(None)
+    call('mvip_mesh_face_openness', ptr(v), ptr(f, _I32), V, F, cbox, ccells, cbounds, ptr(grid.cell_offsets, _I32),
+         ptr(grid.cell_faces, _I32) if grid.n_pairs else none, grid.n_pairs, ptr(d) if K else none, K, float(max_dist),
+         ptr(counts, _I32), ptr(stats, torch.int64) if return_stats else none, stream())
+    out = (counts[0], counts[1], counts[2], counts[3])
+    return out + ((stats,) if return_stats else ())
 
 
 # mesh rasterisation: disparity, face ids and colours per view (beyond the reference, csrc/raster.hip) -------------------------------

@@ -5,7 +5,7 @@ binary PLY (mvip_nerf_amd/mesh.py).  Prints sigma percentiles of the grid (to ch
   python tools/extract_mesh.py CKPT.tar --out mesh.ply [--model mlp|tcnn] [--bound-min x y z --bound-max x y z]
          [--resolution 256] [--threshold 10] [--network fine|coarse] [--precision fp32|split] [--no-colors]
          [--keep-largest K] [--min-component N] [--smooth ITERS] [--simplify STEPS] [--simplify-placement quadric|mean]
-         [--drop-unseen --datadir SCENE [--factor 4]] [--texture N [--texture-from render|dataset] --out mesh.obj]
+         [--drop-interior K] [--drop-unseen --datadir SCENE [--factor 4]] [--texture N [--texture-from render|dataset] --out mesh.obj]
          [--report-error]
   python tools/extract_mesh.py --tsdf --fixture [--iters 1500] --out mesh.ply [--trunc T] [--view-step S] ...
   python tools/extract_mesh.py --tsdf CKPT.tar --datadir SCENE [--factor 4] --out mesh.ply [--trunc T] [--view-step S] ...
@@ -24,6 +24,11 @@ Without the two flags the file is what it was.
 the faces that win a pixel in at least one of them, with the vertices those faces use: the interior sheets and back shells
 of a sigma level set go.  It comes last, after the clean-up.  The cameras are those of --tsdf; without --tsdf they are read
 from --datadir / --factor.  Without the flag the file is what it was.
+
+--drop-interior K casts K spherical-Fibonacci directions (1..255) from every face of the finished mesh (mesh.drop_interior,
+csrc/mesh_raycast.hip) and writes only the faces that see past the mesh in at least one of them, on either side: interior
+shells go, exterior surface stays whether or not a camera saw it.  It needs no cameras; it comes after the clean-up and before
+--drop-unseen.  Without the flag the file is what it was.
 
 --report-error prints what the clean-up cost: the distance report of the finished mesh (after --smooth, --simplify and
 --drop-unseen) against the mesh as first extracted (evaluate.mesh_distance_metrics, csrc/mesh_distance.hip: Chamfer and sampled
@@ -125,6 +130,16 @@ def report_error(a, first, m, lo, hi, res):
     print('error report: ' + json.dumps(rep))
 
 
+def drop_interior(a, m):
+    """--drop-interior on the finished Mesh m: (mesh, seconds)."""
+    if not a.drop_interior:
+        return m, 0.0
+    out, t = _timed(lambda: mesh.drop_interior(m, directions=a.drop_interior))
+    print(f'open in at least one of {a.drop_interior} directions: {m.faces.shape[0]} triangles, {m.verts.shape[0]} vertices '
+          f'-> {out.faces.shape[0]} triangles, {out.verts.shape[0]} vertices  ({t * 1e3:.1f} ms)')
+    return out, t
+
+
 def drop_unseen(a, m, hwf, poses):
     """--drop-unseen on the finished Mesh m: (mesh, seconds)."""
     if not a.drop_unseen:
@@ -215,6 +230,7 @@ def main_tsdf(ap, a, res, dev):
     colors, t_col = (None, 0.0) if a.no_colors else _timed(lambda: mesh.vertex_colors(te, verts, normals, a.network))
     first = mesh.Mesh(verts, faces, normals, colors)
     m, t_clean = clean_up(a, first, lo32, hi32, res)
+    m, _ = drop_interior(a, m)
     m, t_seen = drop_unseen(a, m, hwf, poses)
     report_error(a, first, m, lo32, hi32, res)
     t_tex, t_ply = write_mesh(a, m, te, hwf, poses, near, far, dataset)
@@ -244,6 +260,8 @@ def main(argv=None):
     ap.add_argument('--simplify', type=float, default=0.0, metavar='STEPS',
                     help='cluster the vertices in cells of STEPS times the largest lattice step (0: off)')
     ap.add_argument('--simplify-placement', choices=('quadric', 'mean'), default='quadric')
+    ap.add_argument('--drop-interior', type=int, default=0, metavar='K',
+                    help='write only the faces that see past the mesh in at least one of K Fibonacci directions (0: off)')
     ap.add_argument('--drop-unseen', action='store_true',
                     help='write only the faces some training view sees (cameras: those of --tsdf, else --datadir / --factor)')
     ap.add_argument('--texture', type=int, default=0, metavar='N',
@@ -270,6 +288,8 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if a.smooth < 0 or not a.simplify >= 0:
         ap.error('--smooth and --simplify must be >= 0')
+    if not 0 <= a.drop_interior <= 255:
+        ap.error('--drop-interior: 1..255 directions')
     if not 0 <= a.texture <= 32 or (a.texture and not a.out.endswith('.obj')):
         ap.error('--texture: 1..32 texels, and --out must end in .obj')
     res = a.resolution[0] if len(a.resolution) == 1 else tuple(a.resolution)
@@ -307,6 +327,7 @@ def main(argv=None):
     colors, t_col = (None, 0.0) if a.no_colors else timed(lambda: mesh.vertex_colors(kw, verts, normals, a.network))
     first = mesh.Mesh(verts, faces, normals, colors)
     m, t_clean = clean_up(a, first, a.bound_min, a.bound_max, res)
+    m, _ = drop_interior(a, m)
     t_seen, hwf, cam_poses, near, far, loaded = 0.0, None, None, None, None, None
     if a.drop_unseen or a.texture:
         from mvip_nerf_amd.load_llff import load_llff_data
