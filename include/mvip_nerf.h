@@ -853,6 +853,14 @@ int mvip_distortion_loss(const float *rows, int ncols, const float *z, const flo
  * mvip_harmonic_setup: marks U, copies values to out, lists each image's active tiles, fills state words 0..4.
  * mvip_harmonic_init: u = 0, the right-hand side, r0.z0 partials; max_act >= every image's active tile count
  *   (max_act == 0: nothing launched).
+ * mvip_poisson_init: mvip_harmonic_init with a guidance field (gradient-domain / Poisson blending; between
+ *   mvip_harmonic_setup and mvip_harmonic_iterate, in mvip_harmonic_init's place).  guide [N,H,W] fp32, labels
+ *   [N,H,W] int32, DEVICE.  An edge (p, q), q in N(p), is guided iff labels_p >= 0, labels_q == labels_p and
+ *   guide_p, guide_q are both finite; the right-hand side of p in U is
+ *     sum_{q in N(p), q in K} values_q + sum_{q in N(p), (p,q) guided} (guide_p - guide_q)
+ *   (each sum in fp32 in the order up, left, right, down from 0, the second added to the first).  With no guided
+ *   edge it is mvip_harmonic_init's bit for bit.  NULL values / guide / labels / out / workspace / state, or
+ *   out == values: MVIP_EINVAL.
  * mvip_harmonic_iterate: CG iterations first_iteration .. first_iteration + iterations - 1, two launches each;
  *   a converged image is frozen (it divides nothing) and sets its done word.  0 <= eps < 1.
  * mvip_harmonic_finish: state word 8 = max over U of |sum_{N(p)} out_q - deg out_p| / deg, word 9 = converged.
@@ -864,6 +872,8 @@ int mvip_harmonic_setup(const float *values, const void *masks, int64_t N, int H
                         int *state, void *stream);
 int mvip_harmonic_init(const float *values, int64_t N, int H, int W, float *out, void *workspace, const int *state,
                        int64_t max_act, void *stream);
+int mvip_poisson_init(const float *values, const float *guide, const int *labels, int64_t N, int H, int W, float *out,
+                      void *workspace, const int *state, int64_t max_act, void *stream);
 int mvip_harmonic_iterate(int64_t N, int H, int W, float *out, void *workspace, int *state, int64_t max_act,
                           int first_iteration, int iterations, float eps, void *stream);
 int mvip_harmonic_finish(int64_t N, int H, int W, const float *out, void *workspace, int *state, int64_t max_act, float eps,

@@ -188,6 +188,7 @@ _SIGNATURES = {
     'mvip_harmonic_workspace_bytes': (_i64, [_i64, _int, _int]),
     'mvip_harmonic_setup': (_int, [_c_f, _c_f, _i64, _int, _int, _c_f, _c_f, _c_f, _c_f]),
     'mvip_harmonic_init': (_int, [_c_f, _i64, _int, _int, _c_f, _c_f, _c_f, _i64, _c_f]),
+    'mvip_poisson_init': (_int, [_c_f, _c_f, _c_f, _i64, _int, _int, _c_f, _c_f, _c_f, _i64, _c_f]),
     'mvip_harmonic_iterate': (_int, [_i64, _int, _int, _c_f, _c_f, _c_f, _i64, _int, _int, _flt, _c_f]),
     'mvip_harmonic_finish': (_int, [_i64, _int, _int, _c_f, _c_f, _c_f, _i64, _flt, _c_f]),
     'mvip_mask_dilate2d': (_int, [_c_f, _i64, _int, _int, _c_f, _c_f]),

@@ -7,6 +7,17 @@
 //   right, down in fp32);  output = v bit for bit on K, u on U.  U empty: nothing to do.  U = the whole image: singular, the
 //   image is returned as it is.  Images of a batch are independent problems.
 //
+// The guided (Poisson) variant (ops.poisson_fill, prepare.propagate_reference(blend='poisson'); conventions shared with
+// tests/poisson_numpy.py) adds a guide g [H, W] fp32 and labels l [H, W] int32 per image; U, K, N(p), deg(p) as above.  An edge
+// (p, q), q in N(p), is GUIDED iff l_p >= 0, l_q == l_p, and g_p, g_q are both finite.  For p in U:
+//   deg(p) u_p - sum_{q in N(p) and U} u_q = b_p,   b_p = s_p + t_p,
+//   s_p = sum_{q in N(p) and K} v_q                  (the right-hand side above, the same order and precision),
+//   t_p = sum_{q in N(p), (p, q) guided} (g_p - g_q)  (an fp32 subtraction, then an fp32 addition, up, left, right, down, from 0.f);
+//   output = v bit for bit on K, u on U; U empty / everything as above.  The guide's gradients are trusted inside one source
+//   (one label) only: across a change of label, and where there is none (-1), the edge keeps the harmonic zero-gradient
+//   condition.  With no guided edge t_p = 0.f and b_p is the harmonic fill's bit for bit (s_p is never -0).  Only the
+//   right-hand side differs: poisson_init_kernel stands in for init_kernel, everything else is shared.
+//
 // Method: conjugate gradients with the Jacobi preconditioner (z = r / deg) from u = 0, stopped per image when
 // r.z <= eps^2 r0.z0 on the recursively updated residual.
 //
@@ -186,6 +197,54 @@ __global__ __launch_bounds__(BLOCK) void init_kernel(const float *__restrict__ v
             if (q.x > 0 && !w.um[p - 1]) b += v[p - 1];
             if (q.x < s.W - 1 && !w.um[p + 1]) b += v[p + 1];
             if (y < s.H - 1 && !w.um[p + s.W]) b += v[p + s.W];
+            const float z = b / (float)degree(s, q.x, y);
+            out[p] = 0.f;
+            w.r[p] = b;
+            w.z[p] = z;
+            acc += b * z;
+        }
+    }
+    const float total = block_sum(acc, lds);
+    if (threadIdx.x == 0) w.part_rz[(long long)q.n * s.T + q.j] = total;
+}
+
+// the guided right-hand side (the file header's Poisson variant): init_kernel with b = s + t, t the sum of g_p - g_q over the
+// guided edges.  g and l are read at the pixel and its four neighbours only, every index inside the image.
+__global__ __launch_bounds__(BLOCK) void poisson_init_kernel(const float *__restrict__ v, const float *__restrict__ g,
+                                                            const int *__restrict__ l, const Shape s, float *__restrict__ out, const Work w,
+                                                            const int *__restrict__ state, int max_act) {
+    __shared__ float lds[BLOCK / MVIP_WAVE];
+    const Where q = where(s, w, state, max_act);
+    if (!q.live) return;                         // uniform over the workgroup
+    const long long base = q.n * s.HW;
+    float acc = 0.f;
+    if (q.x < s.W) {
+#pragma unroll
+        for (int i = 0; i < ROWS; ++i) {
+            const int y = q.y0 + i;
+            if (y >= s.H) break;
+            const long long p = base + (long long)y * s.W + q.x;
+            if (!w.um[p]) continue;
+            float b = 0.f;
+            if (y > 0 && !w.um[p - s.W]) b += v[p - s.W];
+            if (q.x > 0 && !w.um[p - 1]) b += v[p - 1];
+            if (q.x < s.W - 1 && !w.um[p + 1]) b += v[p + 1];
+            if (y < s.H - 1 && !w.um[p + s.W]) b += v[p + s.W];
+            const float gp = g[p];
+            const int lp = l[p];
+            float t = 0.f;
+            if (lp >= 0 && finite(gp)) {
+                // the edge (p, o) is guided iff o carries p's label and a finite guide
+                auto edge = [&](long long o) -> void {
+                    const float gq = g[o];
+                    if (l[o] == lp && finite(gq)) t += gp - gq;
+                };
+                if (y > 0) edge(p - s.W);
+                if (q.x > 0) edge(p - 1);
+                if (q.x < s.W - 1) edge(p + 1);
+                if (y < s.H - 1) edge(p + s.W);
+            }
+            b += t;                              // t == 0.f leaves the harmonic b bit for bit (b is never -0)
             const float z = b / (float)degree(s, q.x, y);
             out[p] = 0.f;
             w.r[p] = b;
@@ -419,6 +478,17 @@ extern "C" int mvip_harmonic_init(const float *values, int64_t N, int H, int W, 
     if (!values || !out || !workspace || !state || out == values) return MVIP_EINVAL;
     hipLaunchKernelGGL(harmonic::init_kernel, dim3((unsigned)(N * max_act)), dim3(harmonic::BLOCK), 0, as_stream(stream), values, s,
                        out, harmonic_carve(workspace, N, s), state, (int)max_act);
+    return check_launch();
+}
+
+extern "C" int mvip_poisson_init(const float *values, const float *guide, const int *labels, int64_t N, int H, int W, float *out,
+                                 void *workspace, const int *state, int64_t max_act, void *stream) {
+    harmonic::Shape s;
+    if (!harmonic_shape(N, H, W, s) || !harmonic_grid(N, max_act, s)) return MVIP_EINVAL;
+    if (N == 0 || max_act == 0) return MVIP_OK;
+    if (!values || !guide || !labels || !out || !workspace || !state || out == values) return MVIP_EINVAL;
+    hipLaunchKernelGGL(harmonic::poisson_init_kernel, dim3((unsigned)(N * max_act)), dim3(harmonic::BLOCK), 0, as_stream(stream),
+                       values, guide, labels, s, out, harmonic_carve(workspace, N, s), state, (int)max_act);
     return check_launch();
 }
 

@@ -2090,7 +2090,8 @@ def distortion_loss(weights, z, rows, lindisp=False):
     return _DistortionLoss.apply(_f32c(weights), _f32c(z.detach()), _f32c(rows.detach()), bool(lindisp))
 
 
-# harmonic hole filling and 2D mask dilation (beyond the reference: stands in for --prepare + LaMa; csrc/harmonic.hip) ----------
+# harmonic hole filling, its guided (Poisson) variant and 2D mask dilation (beyond the reference: stands in for --prepare + LaMa;
+# csrc/harmonic.hip) ------------------------------------------------------------------------------------------------------------
 
 def _image_batch(what, t, dtype, name):
     if not torch.is_tensor(t):
@@ -2139,19 +2140,53 @@ def harmonic_fill(values, masks, eps=1e-7, max_iters=None, check_every=32):
     `singular` (every pixel unknown: returned unchanged).  Known finite pixels come back bit for bit.  max_iters=None means
     8 * max(H, W): a cap so that the call always ends (the counts measured are about 2.2 x the hole's diameter).  The flags
     are read back once every `check_every` iterations.  Detached: no autograd."""
-    import numpy as np
-    v = _image_batch('harmonic_fill', values, _F32, 'values')
-    m = _image_batch('harmonic_fill', masks, torch.bool, 'masks')
+    v, m = _fill_operands('harmonic_fill', values, masks)
+    return _cg_fill('harmonic_fill', v, m, eps, max_iters, check_every,
+                    lambda N, H, W, out, ws, state, max_act, st: call('mvip_harmonic_init', ptr(v), N, H, W, out, ws, state, max_act, st))
+
+
+def poisson_fill(values, masks, guide, labels, eps=1e-7, max_iters=None, check_every=32):
+    """harmonic_fill with a guidance field (gradient-domain / Poisson blending; the definition is csrc/harmonic.hip's and
+    tests/poisson_numpy.py's): guide [N, H, W] fp32 and labels [N, H, W] int32 beside values and masks.  An edge between two
+    4-neighbours is guided iff both carry the same label >= 0 and a finite guide; the unknowns then keep the guide's
+    difference across every guided edge and the harmonic zero difference across every other one, with `values` on the known
+    pixels as the boundary.  With no guided edge (labels -1, or a non-finite guide) the result is harmonic_fill's bit for
+    bit.  Returns (filled, info) as harmonic_fill does; the same solver, the same caps, detached."""
+    v, m = _fill_operands('poisson_fill', values, masks)
+    g = _image_batch('poisson_fill', guide, _F32, 'guide')
+    l = _image_batch('poisson_fill', labels, _I32, 'labels')
+    if tuple(g.shape) != tuple(v.shape) or tuple(l.shape) != tuple(v.shape) or g.device != v.device or l.device != v.device:
+        raise ValueError(f'poisson_fill: values {tuple(v.shape)} on {v.device}, guide {tuple(g.shape)} on {g.device}, labels '
+                         f'{tuple(l.shape)} on {l.device}')
+    if not g.is_contiguous():
+        raise ValueError('poisson_fill: guide must be contiguous')
+    l = l.contiguous()                                               # (on values' device, which the shared loop holds to a GPU)
+    return _cg_fill('poisson_fill', v, m, eps, max_iters, check_every,
+                    lambda N, H, W, out, ws, state, max_act, st: call('mvip_poisson_init', ptr(v), ptr(g), ptr(l, _I32), N, H, W, out, ws,
+                                                                      state, max_act, st))
+
+
+def _fill_operands(what, values, masks):
+    v = _image_batch(what, values, _F32, 'values')
+    m = _image_batch(what, masks, torch.bool, 'masks')
     if tuple(v.shape) != tuple(m.shape) or v.device != m.device:
-        raise ValueError(f'harmonic_fill: values {tuple(v.shape)} on {v.device}, masks {tuple(m.shape)} on {m.device}')
+        raise ValueError(f'{what}: values {tuple(v.shape)} on {v.device}, masks {tuple(m.shape)} on {m.device}')
     if not v.is_contiguous():
-        raise ValueError('harmonic_fill: values must be contiguous')
+        raise ValueError(f'{what}: values must be contiguous')
+    return v, m
+
+
+def _cg_fill(what, v, m, eps, max_iters, check_every, init):
+    """The driving loop of harmonic_fill and poisson_fill: set-up, `init` (the right-hand side: the one call in which the two
+    differ; it gets N, H, W, the out / workspace / state pointers, max_act and the stream), iterations with a read-back every
+    check_every, the verdict."""
+    import numpy as np
     N, H, W = v.shape
     eps, check_every = float(eps), int(check_every)
     max_iters = 8 * max(H, W) if max_iters is None else int(max_iters)
     if not 0.0 <= eps < 1.0 or max_iters < 0 or check_every < 1:
-        raise ValueError(f'harmonic_fill: eps {eps} (0 <= eps < 1), max_iters {max_iters} (>= 0), check_every {check_every} (>= 1)')
-    _on_gpu('harmonic_fill', v, m)
+        raise ValueError(f'{what}: eps {eps} (0 <= eps < 1), max_iters {max_iters} (>= 0), check_every {check_every} (>= 1)')
+    _on_gpu(what, v, m)
     m = m.contiguous()
     out = torch.empty_like(v)
     if N == 0:
@@ -2160,14 +2195,14 @@ def harmonic_fill(values, masks, eps=1e-7, max_iters=None, check_every=32):
                      'converged': np.zeros(0, bool), 'singular': np.zeros(0, bool)}
     nbytes = _lib.load().mvip_harmonic_workspace_bytes(N, H, W)
     if nbytes < 0:
-        raise ValueError(f'harmonic_fill: {N} images of {H} x {W} are beyond the kernels\' index range')
+        raise ValueError(f'{what}: {N} images of {H} x {W} are beyond the kernels\' index range')
     ws = torch.empty(nbytes, device=v.device, dtype=torch.uint8)
     state = torch.empty((N, HARMONIC_STATE_WORDS), device=v.device, dtype=_I32)
     st = stream()
     call('mvip_harmonic_setup', ptr(v), ptr(m, torch.bool), N, H, W, ptr(out), ptr(ws, torch.uint8), ptr(state, _I32), st)
     max_act = int(state[:, 0].max().cpu())                           # read-back: sizes the launches over the active tiles
     if max_act > 0:
-        call('mvip_harmonic_init', ptr(v), N, H, W, ptr(out), ptr(ws, torch.uint8), ptr(state, _I32), max_act, st)
+        init(N, H, W, ptr(out), ptr(ws, torch.uint8), ptr(state, _I32), max_act, st)
         k = 0
         while k < max_iters:
             n = min(check_every, max_iters - k)

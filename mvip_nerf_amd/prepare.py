@@ -19,7 +19,9 @@ The third raster, `RGB_inpainted/`, comes from `propagate_reference` (DESIGN.md 
 carried into every other view by backward depth warping (`ops.warp_views`), what no reference sees is filled harmonically,
 and `write_images` writes the files.  The inpainted reference itself can be made here too: `inpaint_views` fills the masks of
 the reference views with texture from the same image (`ops.exemplar_fill`; plausible, not pixel-accurate),
-and `propagate_reference(..., fill='exemplar')` uses the same fill for what no reference sees.
+and `propagate_reference(..., fill='exemplar')` uses the same fill for what no reference sees.  `blend='poisson'` composites in
+the gradient domain instead of pasting (`ops.poisson_fill`): the composite's gradients are kept inside each
+source, the values come from the view's own pixels around the mask, and the step at the mask edge goes.
 
 Which depth is rendered is a choice: `render_disparities(kind='median')` gives 1 / the median termination
 depth of each ray instead of 1 / the expected one, `render_depth_quantiles` several quantiles at once, `spread_mask` the pixels
@@ -221,7 +223,8 @@ def inpaint_views(images, masks, views, method='exemplar', **kw):
     return filled
 
 
-def propagate_reference(images, masks, disparities, poses, focal, ref_views, ref_images=None, tol=0.05, fill=True, **fill_kw):
+def propagate_reference(images, masks, disparities, poses, focal, ref_views, ref_images=None, tol=0.05, fill=True, blend='none',
+                        **fill_kw):
     """Carry the inpainted reference views into every other view through geometry (beyond the reference, whose RGB_inpainted/
     images are independent 2D inpaintings): each masked pixel is lifted with its own disparity and looks its colour up in
     the nearest reference view that sees the same surface (ops.warp_views; the definition is csrc/warp.hip's).
@@ -245,10 +248,27 @@ def propagate_reference(images, masks, disparities, poses, focal, ref_views, ref
     an empty mask), info: ops.harmonic_fill's over the planes 3 n + channel, ops.exemplar_fill's over the views for
     fill='exemplar', None without fill).  ValueError for mismatched shapes, an unknown fill, an empty or invalid ref_views, and
     a plane (a view) with nothing to interpolate (copy) from; RuntimeError naming the views whose
-    fill did not converge, unless allow_unconverged."""
+    fill did not converge, unless allow_unconverged.
+
+    blend='poisson' composites in the gradient domain instead of pasting (Perez, Gangnet, Blake 2003; ops.poisson_fill, the
+    definition is csrc/harmonic.hip's): the composite above becomes a GUIDE whose differences are kept, and the values come from
+    the view's own pixels around the mask.  It needs fill 'harmonic' or 'exemplar' (the solve fills the holes anyway).  The warp
+    runs over the masks dilated by one pixel, so that the ring just outside a mask carries a guide colour and a source too;
+    source, resid, holes and coverage are reported on the masks alone and are blend='none''s.  Labels are the source over the
+    dilated region and -1 elsewhere: a difference is kept only between two pixels of one reference, and across a change of
+    reference, at a hole, and where the ring found no reference the edge is harmonic.  With fill='exemplar' the holes' exemplar
+    texture enters the guide under a label of its own, len(ref_views).  The unknowns are the whole mask of every
+    non-reference view, the boundary values the original images; one ops.poisson_fill call over [3N, H, W] (fill_kw's eps,
+    max_iters, check_every go to it).  The dict gains 'pasted', the images of blend='none'; info is ops.poisson_fill's over
+    the planes 3 n + channel.  Blended values may leave [0, 1]: nothing clamps them here (write_images clips and counts).
+    ValueError for an unknown blend and for blend='poisson' with fill='none'."""
+    if blend not in ('none', 'poisson'):
+        raise ValueError(f'propagate_reference: blend {blend!r}: \'none\' or \'poisson\' expected')
     if isinstance(fill, str) and fill not in FILLS:
         raise ValueError(f'propagate_reference: fill {fill!r}: True / \'harmonic\', \'exemplar\' or False / \'none\' expected')
     fill = FILLS[fill if isinstance(fill, str) else bool(fill)]
+    if blend == 'poisson' and fill == 'none':
+        raise ValueError('propagate_reference: blend \'poisson\' fills the holes by its solve: fill \'harmonic\' or \'exemplar\' expected')
     allow_unconverged = bool(fill_kw.pop('allow_unconverged', False))
     device = images.device if torch.is_tensor(images) and images.is_cuda else torch.device('cuda')
     shape = lambda a: tuple(a.shape) if hasattr(a, 'shape') else type(a).__name__
@@ -275,8 +295,19 @@ def propagate_reference(images, masks, disparities, poses, focal, ref_views, ref
     order = torch.from_numpy(reference_order(pose.cpu().numpy(), refs)).to(device)
     warp_mask = msk.clone()
     warp_mask[ridx] = False                                   # a reference view is not warped into
-    rgb, source, resid = ops.warp_views(disp, pose, warp_mask, src_rgb, disp[ridx].contiguous(), pose[ridx].contiguous(),
+    wide = None
+    if blend == 'poisson':
+        wide = ops.mask_dilate2d(warp_mask, 1)                # the masks and the ring just outside them; empty for a reference view
+        solver_kw = {k: fill_kw[k] for k in ('eps', 'max_iters', 'check_every') if k in fill_kw}
+        if fill == 'exemplar':
+            fill_kw = {k: v for k, v in fill_kw.items() if k not in solver_kw}
+    rgb, source, resid = ops.warp_views(disp, pose, warp_mask if wide is None else wide, src_rgb, disp[ridx].contiguous(), pose[ridx].contiguous(),
                                         float(focal), order=order.contiguous(), tol=tol)
+    if wide is not None:                                      # a per-pixel gather: on the masks it is the warp over the masks
+        rgb_wide, source_wide = rgb, source
+        zero = torch.zeros((), device=device)
+        rgb, resid = torch.where(warp_mask[..., None], rgb, zero), torch.where(warp_mask, resid, zero)
+        source = torch.where(warp_mask, source, torch.full((), -1, device=device, dtype=source.dtype))
     out = torch.where((source >= 0)[..., None], rgb, img)
     for k, v in enumerate(refs):
         out[v] = src_rgb[k]
@@ -302,7 +333,30 @@ def propagate_reference(images, masks, disparities, poses, focal, ref_views, ref
     n_mask = msk.sum((1, 2)).cpu().numpy().astype(np.float64)
     n_src = (msk & (source >= 0)).sum((1, 2)).cpu().numpy().astype(np.float64)
     coverage = np.where(n_mask > 0, n_src / np.maximum(n_mask, 1.0), 1.0)
-    return {'images': out.contiguous(), 'source': source, 'resid': resid, 'holes': holes, 'coverage': coverage, 'info': info}
+    result = {'images': out.contiguous(), 'source': source, 'resid': resid, 'holes': holes, 'coverage': coverage, 'info': info}
+    if wide is None:
+        return result
+    pasted = result['images']
+    labels = source_wide.clone()                              # -1 off the dilated region: the warp leaves it so
+    guide = rgb_wide
+    if fill == 'exemplar':
+        labels[holes] = len(refs)
+        guide = torch.where(holes[..., None], pasted, guide)
+    planes = lambda a: a.permute(0, 3, 1, 2).reshape(3 * N, H, W).contiguous()
+    over_channels = lambda a: a[:, None].expand(N, 3, H, W).reshape(3 * N, H, W).contiguous()
+    filled, info = ops.poisson_fill(planes(img), over_channels(warp_mask), planes(guide), over_channels(labels), **solver_kw)
+    singular = sorted({int(p) // 3 for p in np.nonzero(info['singular'])[0]})
+    if singular:
+        raise ValueError(f'propagate_reference: views {singular} have no known pixel to blend their masks from')
+    bad = sorted({int(p) // 3 for p in np.nonzero(~info['converged'])[0]})
+    if bad and not allow_unconverged:
+        raise RuntimeError(f'propagate_reference: the blend of views {bad} did not converge (raise max_iters, or pass '
+                           f'allow_unconverged=True)')
+    blended = torch.where(warp_mask[..., None], filled.reshape(N, 3, H, W).permute(0, 2, 3, 1), img)
+    for k, v in enumerate(refs):
+        blended[v] = src_rgb[k]
+    result.update(images=blended.contiguous(), pasted=pasted, info=info)
+    return result
 
 
 def write_images(root, names, images):
