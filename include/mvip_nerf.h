@@ -1200,6 +1200,60 @@ int mvip_ray_quantile_depth(const float *z, const float *weights, int64_t B, int
 int mvip_depth_consistency(const float *disp, const float *pose, int V, int H, int W, float focal, float tol, int *agree,
                            int *violated, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Topology of an indexed triangle mesh (beyond the reference, which has no mesh at all: no entry point has a reference call
+ * site; csrc/mesh_topology.hip, ops.mesh_edge_table / mesh_components / mesh_boundary_loops / mesh_cap_loops,
+ * mesh.topology / keep_components / boundary_loops / close_holes).  The definitions are stated once, in the header comment of
+ * csrc/mesh_topology.hip, and restated in tests/mesh_topology_numpy.py.  faces [F,3] int32, 3 F <= 2^31 - 1; half-edge
+ * h = 3 f + k runs from faces[f,k] to faces[f,(k+1)%3].  Integer work only (plus one fp64 sum per capped loop): no float
+ * atomics, every output bit-reproducible.  The lists are those of mvip_mesh_corner_table, built by the caller; the `*_wg`
+ * workspaces hold mvip_mesh_rank_groups(n) words for the n items ranked.  A negative count, 3 F > 2^31 - 1, an output count
+ * above its bound or a NULL operand that a non-zero count makes necessary: MVIP_EINVAL before any device call.  F = 0:
+ * MVIP_OK, nothing launched (the caller returns empty tensors).  Every launch goes on the caller's stream.
+ * mvip_mesh_topology_keys: keys [3F] = min(a, b) of each half-edge, -1 for the half-edges of a face that names a vertex
+ *   twice or an index outside [0, V); flag[0] = 1 iff such an index exists, else 0.
+ * mvip_mesh_topology_edges_find: offsets [V+1] / items: the lists of `keys` over V lists.  Per half-edge: rep [3F] the lowest
+ *   half-edge of its edge (-1: none), hcount / hforward [3F] the edge's half-edges and those of them that run lo -> hi,
+ *   twin [3F]; rank [3F] = representatives below h, total[0] = E: the caller's one read.
+ * mvip_mesh_topology_edges_emit: edge_of [3F], edges [E,2] = (lo, hi), first / count / forward [E].
+ * mvip_mesh_topology_components_label: connectivity 0 = 'edge', 1 = 'vertex'; offsets / corners: the corner table.  parent
+ *   [F] = the lowest face of each face's component (-1: degenerate), is_root / rank [F]: workspace, total[0] = C.
+ * mvip_mesh_topology_components_emit: labels [F] (1..C by lowest face, 0: degenerate), table [C,6] = faces, vertices, edges,
+ *   boundary, non-manifold, inconsistent edges.
+ * mvip_mesh_topology_loops_label: ends [V]: workspace; next [3F]; parent [3F] = the lowest half-edge of each boundary
+ *   half-edge's loop (-1 off the boundary); is_root / rank [3F]: workspace; total[0] = L.
+ * mvip_mesh_topology_loops_emit: loop_of [3F] (-1 off the boundary), first / sizes / closed [L].
+ * mvip_mesh_topology_cap_plan: capped [L] = closed and 3 <= size <= max_edges; keys [3F] = the loop of a half-edge of a capped
+ *   loop, else -1; loop_rank [L] / he_rank [3F] = capped loops / cap faces below; totals[0] = caps, totals[1] = cap faces.
+ * mvip_mesh_topology_cap_emit: loop_offsets [L+1] / loop_items: the lists of those keys over L lists.  new_verts [n_caps,3]
+ *   (fp64 mean of the origins in list order, rounded once), new_colors [n_caps,3] or NULL with colors NULL (integer mean
+ *   (2 sum + n) / (2 n)), new_faces [n_cap_faces,3] = (b, a, V + cap number) in ascending half-edge order. */
+int mvip_mesh_topology_keys(const int *faces, int64_t n_faces, int64_t n_verts, int *keys, int *flag, void *stream);
+int mvip_mesh_topology_edges_find(const int *faces, int64_t n_faces, int64_t n_verts, const int *keys, const int *offsets,
+                                  const int *items, int *rep, int *hcount, int *hforward, int *twin, int *wg, int *rank,
+                                  int64_t *total, void *stream);
+int mvip_mesh_topology_edges_emit(const int *faces, int64_t n_faces, const int *rep, const int *hcount, const int *hforward,
+                                  const int *rank, int64_t n_edges, int *edge_of, int *edges, int *first, int *count,
+                                  int *forward, void *stream);
+int mvip_mesh_topology_components_label(const int *faces, int64_t n_faces, int64_t n_verts, int connectivity, const int *rep,
+                                        const int *offsets, const int *corners, int *parent, int *is_root, int *wg, int *rank,
+                                        int64_t *total, void *stream);
+int mvip_mesh_topology_components_emit(const int *faces, int64_t n_faces, int64_t n_verts, const int *parent, const int *rank,
+                                       int64_t n_components, const int *rep, const int *hcount, const int *hforward,
+                                       const int *offsets, const int *corners, int *labels, int *table, void *stream);
+int mvip_mesh_topology_loops_label(const int *faces, int64_t n_faces, int64_t n_verts, const int *rep, const int *hcount,
+                                   const int *offsets, const int *corners, int *ends, int *next, int *parent, int *is_root,
+                                   int *wg, int *rank, int64_t *total, void *stream);
+int mvip_mesh_topology_loops_emit(int64_t n_faces, const int *parent, const int *rank, const int *next, int64_t n_loops,
+                                  int *loop_of, int *first, int *sizes, int *closed, void *stream);
+int mvip_mesh_topology_cap_plan(int64_t n_faces, const int *loop_of, int64_t n_loops, const int *sizes, const int *closed,
+                                int64_t max_edges, int *capped, int *keys, int *loop_wg, int *loop_rank, int *he_wg,
+                                int *he_rank, int64_t *totals, void *stream);
+int mvip_mesh_topology_cap_emit(const float *verts, const void *colors, const int *faces, int64_t n_verts, int64_t n_faces,
+                                int64_t n_loops, const int *keys, const int *capped, const int *loop_rank, const int *he_rank,
+                                const int *loop_offsets, const int *loop_items, int64_t n_caps, int64_t n_cap_faces,
+                                float *new_verts, void *new_colors, int *new_faces, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -242,6 +242,15 @@ _SIGNATURES = {
                                        _c_f, _c_f, _i64, _c_f, _int, _flt, _c_f, _c_f, _c_f]),
     'mvip_ray_quantile_depth': (_int, [_c_f, _c_f, _i64, _int, ctypes.POINTER(_flt), _int, _c_f, _c_f]),
     'mvip_depth_consistency': (_int, [_c_f, _c_f, _int, _int, _int, _flt, _flt, _c_f, _c_f, _c_f]),
+    'mvip_mesh_topology_keys': (_int, [_c_f, _i64, _i64, _c_f, _c_f, _c_f]),
+    'mvip_mesh_topology_edges_find': (_int, [_c_f, _i64, _i64] + [_c_f] * 11),
+    'mvip_mesh_topology_edges_emit': (_int, [_c_f, _i64, _c_f, _c_f, _c_f, _c_f, _i64] + [_c_f] * 6),
+    'mvip_mesh_topology_components_label': (_int, [_c_f, _i64, _i64, _int] + [_c_f] * 9),
+    'mvip_mesh_topology_components_emit': (_int, [_c_f, _i64, _i64, _c_f, _c_f, _i64] + [_c_f] * 8),
+    'mvip_mesh_topology_loops_label': (_int, [_c_f, _i64, _i64] + [_c_f] * 12),
+    'mvip_mesh_topology_loops_emit': (_int, [_i64, _c_f, _c_f, _c_f, _i64] + [_c_f] * 5),
+    'mvip_mesh_topology_cap_plan': (_int, [_i64, _c_f, _i64, _c_f, _c_f, _i64] + [_c_f] * 8),
+    'mvip_mesh_topology_cap_emit': (_int, [_c_f, _c_f, _c_f, _i64, _i64, _i64] + [_c_f] * 6 + [_i64, _i64] + [_c_f] * 4),
 }
 
 # every symbol include/mvip_nerf.h declares; tests check the built library exports all of them

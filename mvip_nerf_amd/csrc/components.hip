@@ -25,12 +25,14 @@
 //   cc_select:   labels + keep table -> bits of the kept components, one ballot per 64 labels.
 #include "bitgrid_device.h"
 #include "compact_device.h"
+#include "unionfind_device.h"
 
 namespace mvip {
 namespace cc {
 
 using namespace bitgrid;
 using namespace compact;
+using namespace unionfind;             // load_parent, find, unite
 
 constexpr int MAX_AXIS = 768;                // 3 * 768^3 < 2^31; the lattice limit of csrc/mcubes.hip
 
@@ -53,30 +55,6 @@ __global__ __launch_bounds__(BLOCK) void cc_pack_kernel(const float *__restrict_
                                                        unsigned *__restrict__ words, int nwords) {
     const int l = blockIdx.x * BLOCK + threadIdx.x;
     store_wave_bits(l < n && values[l] >= thr, l, words, nwords);
-}
-
-__device__ __forceinline__ int load_parent(const int *parent, int a) {
-    return __hip_atomic_load(parent + a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// parent[x] <= x always, so the walk ends
-__device__ __forceinline__ int find(const int *parent, int a) {
-    int p = load_parent(parent, a);
-    while (p != a) {
-        a = p;
-        p = load_parent(parent, a);
-    }
-    return a;
-}
-__device__ __forceinline__ void unite(int *parent, int a, int b) {
-    for (;;) {
-        a = find(parent, a);
-        b = find(parent, b);
-        if (a == b) return;
-        if (a < b) { const int t = a; a = b; b = t; }
-        const int old = atomicMin(parent + a, b);            // a was a root when read; if it no longer is, parent[a] = min(old, b)
-        if (old == a) return;                                //   and the tie between old and b is made next
-        a = old;
-    }
 }
 
 __global__ __launch_bounds__(BLOCK) void cc_init_kernel(const unsigned *__restrict__ words, int n, int nz,

@@ -703,6 +703,90 @@ def drop_interior(mesh, directions=32, two_sided=True, max_dist=None):
     return keep_faces(mesh, (fo + bo > 0) if two_sided else (fo > 0))
 
 
+# ---- topology (csrc/mesh_topology.hip): which faces belong together, is the surface closed, where are its holes ----------------
+TOPOLOGY_COLUMNS = ('faces', 'vertices', 'edges', 'boundary_edges', 'non_manifold_edges', 'inconsistent_edges')
+
+
+def topology(mesh, connectivity='edge'):
+    """A report on the surface as a dict: the totals of TOPOLOGY_COLUMNS (vertices: those some non-degenerate face references),
+    `components` (their number) and `per_component` (a list of dicts with the same columns plus closed / oriented / euler /
+    genus, in label order = by lowest face), `degenerate_faces`, `closed` (no boundary and no non-manifold edge), `oriented` (no
+    edge whose two faces run it the same way, none with three or more faces), `euler` = V - E + F, `genus` = (2 - euler) / 2 of
+    a component where it is closed and oriented, else None (the mesh's genus: the sum over its components, None if any is
+    None), `loops` and `closed_loops` (boundary_loops).  connectivity 'edge' or 'vertex' (ops.mesh_components)."""
+    V = int(mesh.verts.shape[0])
+    labels, table = ops.mesh_components(mesh.faces, V, connectivity)
+    loops = ops.mesh_boundary_loops(mesh.faces, V)
+    t = table.cpu().numpy().astype(np.int64).reshape(-1, 6)
+
+    def describe(row):
+        d = dict(zip(TOPOLOGY_COLUMNS, (int(x) for x in row)))
+        d['closed'] = d['boundary_edges'] == 0 and d['non_manifold_edges'] == 0
+        d['oriented'] = d['inconsistent_edges'] == 0 and d['non_manifold_edges'] == 0
+        d['euler'] = d['vertices'] - d['edges'] + d['faces']
+        return d
+
+    per = [describe(r) for r in t]
+    for d in per:
+        d['genus'] = (2 - d['euler']) // 2 if d['closed'] and d['oriented'] else None
+    out = describe(t.sum(0))
+    out['genus'] = sum(d['genus'] for d in per) if all(d['genus'] is not None for d in per) else None
+    out.update(components=len(per), per_component=per, degenerate_faces=int((labels == 0).sum()),
+               loops=int(loops.first.shape[0]), closed_loops=int(loops.closed.sum()) if loops.closed.shape[0] else 0)
+    return out
+
+
+def keep_components(mesh, largest=None, min_faces=None, containing=None, connectivity='edge'):
+    """The mesh with only the faces of the kept components (ops.mesh_components, keep_faces): largest = k keeps the k
+    components with the most faces (ties: the lower label = the lower first face), min_faces = m those of at least m faces, a
+    component must meet both where both are given (ops.component_criteria / component_keep_table, as remove_floaters on the
+    lattice); containing: [N, 3] points, the component of each point's closest face (ops.mesh_closest_point) is kept in any
+    case.  Kept faces and vertices keep their order and their bits; degenerate faces go.  ValueError for no criterion."""
+    largest, min_faces = ops.component_criteria('keep_components', largest, min_faces, other=containing is not None,
+                                                size_name='min_faces')
+    labels, table = ops.mesh_components(mesh.faces, int(mesh.verts.shape[0]), connectivity)
+    also = None
+    if containing is not None and mesh.faces.shape[0]:
+        pts = torch.as_tensor(containing, dtype=torch.float32).reshape(-1, 3).to(mesh.verts.device).contiguous()
+        if pts.shape[0]:
+            face = ops.mesh_closest_point(pts, mesh.verts, mesh.faces)[0]
+            also = labels[face[face >= 0].to(torch.int64)].cpu().numpy()
+    keep = ops.component_keep_table(table[:, 0].cpu().numpy(), largest, min_faces, also)
+    return keep_faces(mesh, torch.from_numpy(keep).to(mesh.faces.device)[labels.to(torch.int64)].bool())
+
+
+def boundary_loops(mesh):
+    """ops.MeshBoundaryLoops(loop_of [3F], next [3F], first [L], sizes [L], closed [L]) of the mesh's boundary: the holes of a
+    surface that should be closed, the rim of one that is a sheet.  See ops.mesh_boundary_loops."""
+    return ops.mesh_boundary_loops(mesh.faces, int(mesh.verts.shape[0]))
+
+
+def close_holes(mesh, max_edges=64):
+    """(mesh', capped, left): the mesh with every closed boundary loop of 3..max_edges edges capped by a fan round the loop's
+    centroid (ops.mesh_cap_loops), the number of loops capped and the number left open.  The caps are appended: the old
+    vertices, faces, colours and normals keep their rows bit for bit; a new vertex takes the mean colour of its loop, and
+    where the mesh carries normals its row is that of ops.mesh_vertex_normals of the capped mesh.  The new faces are wound
+    against the boundary, so a consistently oriented mesh stays so.
+
+    What a centroid fan is NOT: a hole filler for large or strongly non-planar holes.  The centroid of a long or bent loop can
+    lie far from any sensible surface (outside the shape for a C-shaped rim), the fan can fold over itself or cut through the
+    mesh, and its triangles are slivers when the loop is long.  It is right for the small, nearly flat cuts that dropping
+    unseen or interior faces leaves; max_edges is there to keep it to those, and loops that touch themselves at a vertex
+    (not closed) are never capped."""
+    new_v, new_c, new_f, capped = ops.mesh_cap_loops(mesh.verts, mesh.faces, mesh.colors, max_edges)
+    n_capped = int(capped.sum()) if capped.shape[0] else 0
+    left = int(capped.shape[0]) - n_capped
+    if n_capped == 0:
+        return mesh, 0, left
+    verts = torch.cat([mesh.verts, new_v]).contiguous()
+    faces = torch.cat([mesh.faces, new_f]).contiguous()
+    colors = None if mesh.colors is None else torch.cat([mesh.colors, new_c]).contiguous()
+    normals = mesh.normals
+    if normals is not None:
+        normals = torch.cat([normals, ops.mesh_vertex_normals(verts, faces)[mesh.verts.shape[0]:]]).contiguous()
+    return Mesh(verts, faces, normals, colors), n_capped, left
+
+
 Texture = collections.namedtuple('Texture', ['image', 'uv', 'seen', 'texels'])
 
 

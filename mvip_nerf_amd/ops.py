@@ -7,6 +7,7 @@ forward, the data gradient and the weight gradient (`_LinearCM`; `MVIP_SKINNY_LI
 timing only), the SDS networks the split-precision kernels.  What stock torch GPU ops remain are tensor allocation,
 concatenations and a few elementwise glue ops; they are named where they occur.
 """
+import collections
 import weakref
 
 import torch
@@ -2809,6 +2810,196 @@ def mesh_cluster(verts, faces, colors, origin, cell, placement='quadric', dedupe
          ptr(crank, _I32), V, F2, V2, ptr(cov, _I32), ptr(out_v) if V2 else none, ptr(out_c, torch.uint8) if V2 else none,
          ptr(out_f, _I32) if F2 else none, st)
     return out_v, out_f, out_c, cov
+
+
+# mesh topology: edge table, face components, boundary loops, hole caps (beyond the reference, csrc/mesh_topology.hip) ---------
+# The definitions are csrc/mesh_topology.hip's and tests/mesh_topology_numpy.py's.  There is no CPU path.
+
+MESH_CONNECTIVITIES = ('edge', 'vertex')
+MeshEdgeTable = collections.namedtuple('MeshEdgeTable', 'edge_of edges first count forward twin')
+MeshBoundaryLoops = collections.namedtuple('MeshBoundaryLoops', 'loop_of next first sizes closed')
+
+
+def _topology_faces(what, faces, n_verts):
+    n_verts = int(n_verts)
+    if n_verts < 0 or n_verts > 2 ** 31 - 2:
+        raise ValueError(f'{what}: n_verts must be in 0..2^31 - 2, got {n_verts}')
+    if not torch.is_tensor(faces):
+        raise ValueError(f'{what}: faces must be a tensor on the GPU, got {type(faces).__name__}')
+    if faces.dtype != _I32:
+        raise ValueError(f'{what}: faces must be {_I32}, got {faces.dtype}')
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f'{what}: faces must be [F, 3], got {tuple(faces.shape)}')
+    if not faces.is_cuda:
+        raise ValueError(f'{what}: tensors on the GPU expected (the HIP path has no CPU path)')
+    if not faces.is_contiguous():
+        raise ValueError(f'{what}: every operand must be contiguous')
+    if 3 * faces.shape[0] > 2 ** 31 - 1:
+        raise ValueError(f'{what}: {faces.shape[0]} faces exceed int32 half-edge indices')
+    if faces.shape[0] and n_verts == 0:
+        raise ValueError(f'{what}: a face index lies outside [0, 0)')
+    return faces.detach(), n_verts
+
+
+def _rank_wg(n, dev):
+    return torch.empty(max(1, _lib.load().mvip_mesh_rank_groups(n)), device=dev, dtype=_I32)
+
+
+class _HalfEdges:
+    """The per-half-edge state every topology op starts from (F > 0): rep, hcount, hforward, twin, rank [3F] and E."""
+
+    def __init__(self, what, f, V):
+        F = int(f.shape[0])
+        dev = f.device
+        n = 3 * F
+        st = stream()
+        i32 = lambda *shape: torch.empty(shape, device=dev, dtype=_I32)
+        keys, flag = i32(n), i32(1)
+        call('mvip_mesh_topology_keys', ptr(f, _I32), F, V, ptr(keys, _I32), ptr(flag, _I32), st)
+        offsets, items, _ = _mesh_lists(keys, V)          # the lists' own flag only says that some key is -1
+        self.rep, self.hcount, self.hforward, self.twin, self.rank = i32(n), i32(n), i32(n), i32(n), i32(n)
+        meta = torch.empty(1, device=dev, dtype=torch.int64)
+        p = lambda t: ptr(t, _I32)
+        call('mvip_mesh_topology_edges_find', p(f), F, V, p(keys), p(offsets), p(items), p(self.rep), p(self.hcount),
+             p(self.hforward), p(self.twin), p(_rank_wg(n, dev)), p(self.rank), ptr(meta, torch.int64), st)
+        if int(flag.cpu()):
+            raise ValueError(f'{what}: a face index lies outside [0, {V})')
+        self.E = int(meta.cpu())
+        self.f, self.F, self.V = f, F, V
+
+    def edge_table(self):
+        dev, E, n = self.f.device, self.E, 3 * self.F
+        i32 = lambda *shape: torch.empty(shape, device=dev, dtype=_I32)
+        edge_of, edges, first, count, forward = i32(n), i32(E, 2), i32(E), i32(E), i32(E)
+        p = lambda t: ptr(t, _I32) if t.numel() else ptr(None)
+        call('mvip_mesh_topology_edges_emit', p(self.f), self.F, p(self.rep), p(self.hcount), p(self.hforward), p(self.rank), E,
+             p(edge_of), p(edges), p(first), p(count), p(forward), stream())
+        return MeshEdgeTable(edge_of, edges, first, count, forward, self.twin)
+
+
+def _empty_i32(dev, *shape):
+    return torch.empty(shape, device=dev, dtype=_I32)
+
+
+def mesh_edge_table(faces, n_verts):
+    """The edge table of faces [F, 3] int32 on the device (csrc/mesh_topology.hip): MeshEdgeTable(edge_of [3F], edges [E, 2] =
+    (lo, hi), first [E], count [E], forward [E], twin [3F]), all int32.  Half-edge h = 3 f + k runs from faces[f, k] to
+    faces[f, (k + 1) % 3]; an edge is the set of half-edges with the same unordered endpoints; edges are numbered by their
+    lowest half-edge `first`; count = its half-edges, forward = those that run lo -> hi; twin = the other half-edge of an edge
+    with exactly two, else -1.  count 1: boundary; 2 with forward 1: interior; 2 otherwise: inconsistently oriented; >= 3:
+    non-manifold.  A face that names a vertex twice has edge_of = twin = -1.  F = 0 or V = 0: empty tensors, nothing
+    launched.  ValueError for a face index outside [0, V).  Reads back the flag and E."""
+    what = 'mesh_edge_table'
+    f, V = _topology_faces(what, faces, n_verts)
+    if f.shape[0] == 0:
+        e = lambda *s: _empty_i32(f.device, *s)
+        return MeshEdgeTable(e(0), e(0, 2), e(0), e(0), e(0), e(0))
+    return _HalfEdges(what, f, V).edge_table()
+
+
+def _mesh_components(what, he, connectivity):
+    f, F, V = he.f, he.F, he.V
+    dev = f.device
+    st = stream()
+    p = lambda t: ptr(t, _I32) if t.numel() else ptr(None)
+    offsets, corners = mesh_corner_table(f, V)
+    parent, is_root, rank = _empty_i32(dev, F), _empty_i32(dev, F), _empty_i32(dev, F)
+    total = torch.empty(1, device=dev, dtype=torch.int64)
+    call('mvip_mesh_topology_components_label', p(f), F, V, MESH_CONNECTIVITIES.index(connectivity), p(he.rep), p(offsets),
+         p(corners), p(parent), p(is_root), p(_rank_wg(F, dev)), p(rank), ptr(total, torch.int64), st)
+    C = int(total.cpu())
+    labels, table = _empty_i32(dev, F), _empty_i32(dev, C, 6)
+    call('mvip_mesh_topology_components_emit', p(f), F, V, p(parent), p(rank), C, p(he.rep), p(he.hcount), p(he.hforward),
+         p(offsets), p(corners), p(labels), p(table), st)
+    return labels, table
+
+
+def mesh_components(faces, n_verts, connectivity='edge'):
+    """Connected components of the faces [F, 3] int32 of a mesh: (labels [F] int32, table [C, 6] int32).  connectivity 'edge':
+    two faces that share an edge (unordered endpoints) are connected; 'vertex': two faces that share a vertex.  labels are
+    1..C in order of each component's lowest face index (ops.grid_components' convention), 0 for a face that names a vertex
+    twice.  table columns: faces, vertices, edges, boundary edges (one face), non-manifold edges (three or more), inconsistently
+    oriented edges (two faces that run it the same way); V - E + F of a component is table[:, 1] - table[:, 2] + table[:, 0].
+    F = 0 or V = 0: empty tensors, nothing launched.  ValueError for another connectivity or a face index outside [0, V)."""
+    what = 'mesh_components'
+    if connectivity not in MESH_CONNECTIVITIES:
+        raise ValueError(f"{what}: connectivity must be 'edge' or 'vertex', got {connectivity!r}")
+    f, V = _topology_faces(what, faces, n_verts)
+    if f.shape[0] == 0:
+        return _empty_i32(f.device, 0), _empty_i32(f.device, 0, 6)
+    return _mesh_components(what, _HalfEdges(what, f, V), connectivity)
+
+
+def _mesh_boundary_loops(he):
+    f, F, V = he.f, he.F, he.V
+    dev = f.device
+    n = 3 * F
+    st = stream()
+    p = lambda t: ptr(t, _I32) if t.numel() else ptr(None)
+    offsets, corners = mesh_corner_table(f, V)
+    ends, nxt, parent, is_root, rank = (_empty_i32(dev, V), _empty_i32(dev, n), _empty_i32(dev, n), _empty_i32(dev, n),
+                                        _empty_i32(dev, n))
+    total = torch.empty(1, device=dev, dtype=torch.int64)
+    call('mvip_mesh_topology_loops_label', p(f), F, V, p(he.rep), p(he.hcount), p(offsets), p(corners), p(ends), p(nxt), p(parent),
+         p(is_root), p(_rank_wg(n, dev)), p(rank), ptr(total, torch.int64), st)
+    L = int(total.cpu())
+    loop_of, first, sizes, closed = _empty_i32(dev, n), _empty_i32(dev, L), _empty_i32(dev, L), _empty_i32(dev, L)
+    call('mvip_mesh_topology_loops_emit', F, p(parent), p(rank), p(nxt), L, p(loop_of), p(first), p(sizes), p(closed), st)
+    return MeshBoundaryLoops(loop_of, nxt, first, sizes, closed)
+
+
+def mesh_boundary_loops(faces, n_verts):
+    """The boundary loops of faces [F, 3] int32: MeshBoundaryLoops(loop_of [3F], next [3F], first [L], sizes [L], closed [L]),
+    all int32.  A boundary half-edge is the only half-edge of its edge.  next[h] of a boundary half-edge a -> b is the boundary
+    half-edge that starts at b if exactly one starts and exactly one ends there, else -1 (a pinch vertex, where the walk is
+    ambiguous); -1 for every other half-edge.  Loops are the chains of next, numbered by their lowest half-edge `first`;
+    loop_of is -1 off the boundary; closed[l] = 1 iff every member has a next, and such a loop is a simple cycle.  F = 0 or
+    V = 0: empty tensors, nothing launched.  ValueError for a face index outside [0, V)."""
+    what = 'mesh_boundary_loops'
+    f, V = _topology_faces(what, faces, n_verts)
+    if f.shape[0] == 0:
+        e = lambda *s: _empty_i32(f.device, *s)
+        return MeshBoundaryLoops(e(0), e(0), e(0), e(0), e(0))
+    return _mesh_boundary_loops(_HalfEdges(what, f, V))
+
+
+def mesh_cap_loops(verts, faces, colors, max_edges):
+    """Centroid-fan caps of the small boundary loops of a mesh: (new_verts [N, 3] fp32, new_colors uint8 [N, 3] or None,
+    new_faces [M, 3] int32, capped [L] int32).  A loop of mesh_boundary_loops is capped iff it is closed and has 3..max_edges
+    half-edges.  Per capped loop one new vertex, the mean of the loop's origin vertices (fp64 sum in ascending half-edge
+    order, rounded to fp32 once; colours: exact integer means), numbered V, V + 1, ... in loop order; per boundary half-edge
+    a -> b of it the face (b, a, new vertex), in ascending half-edge order: reversed, so a consistently oriented mesh stays
+    consistent.  The capped mesh is cat(verts, new_verts), cat(faces, new_faces).  F = 0 or V = 0: empty tensors, nothing
+    launched.  ValueError for max_edges < 3 or a face index outside [0, V)."""
+    what = 'mesh_cap_loops'
+    v, f, *c = _mesh_operands(what, verts, faces, colors)
+    c = c[0] if c else None
+    if int(max_edges) != max_edges or int(max_edges) < 3:
+        raise ValueError(f'{what}: max_edges must be an integer >= 3, got {max_edges!r}')
+    max_edges = min(int(max_edges), 2 ** 31 - 1)
+    f, V = _topology_faces(what, f, v.shape[0])
+    dev = v.device
+    F = int(f.shape[0])
+    none_c = None if c is None else torch.empty((0, 3), device=dev, dtype=torch.uint8)
+    if F == 0:
+        return torch.empty((0, 3), device=dev, dtype=_F32), none_c, _empty_i32(dev, 0, 3), _empty_i32(dev, 0)
+    loops = _mesh_boundary_loops(_HalfEdges(what, f, V))
+    L, n = int(loops.first.shape[0]), 3 * F
+    st = stream()
+    p = lambda t: ptr(t, _I32) if t.numel() else ptr(None)
+    capped, keys, loop_rank, he_rank = _empty_i32(dev, L), _empty_i32(dev, n), _empty_i32(dev, L), _empty_i32(dev, n)
+    totals = torch.empty(2, device=dev, dtype=torch.int64)
+    call('mvip_mesh_topology_cap_plan', F, p(loops.loop_of), L, p(loops.sizes), p(loops.closed), max_edges, p(capped), p(keys),
+         p(_rank_wg(L, dev)), p(loop_rank), p(_rank_wg(n, dev)), p(he_rank), ptr(totals, torch.int64), st)
+    n_caps, n_cap_faces = (int(x) for x in totals.cpu())
+    new_v = torch.empty((n_caps, 3), device=dev, dtype=_F32)
+    new_c = None if c is None else torch.empty((n_caps, 3), device=dev, dtype=torch.uint8)
+    new_f = _empty_i32(dev, n_cap_faces, 3)
+    if n_caps:
+        loop_off, loop_items, _ = _mesh_lists(keys, L)
+        call('mvip_mesh_topology_cap_emit', ptr(v), ptr(c, torch.uint8), p(f), V, F, L, p(keys), p(capped), p(loop_rank), p(he_rank),
+             p(loop_off), p(loop_items), n_caps, n_cap_faces, ptr(new_v), ptr(new_c, torch.uint8), p(new_f), st)
+    return new_v, new_c, new_f, capped
 
 
 # mesh-to-mesh distance: closest-point queries on a grid of face lists, surface samples (beyond the reference, csrc/mesh_distance.hip)

@@ -6,7 +6,7 @@ binary PLY (mvip_nerf_amd/mesh.py).  Prints sigma percentiles of the grid (to ch
          [--resolution 256] [--threshold 10] [--network fine|coarse] [--precision fp32|split] [--no-colors]
          [--keep-largest K] [--min-component N] [--smooth ITERS] [--simplify STEPS] [--simplify-placement quadric|mean]
          [--drop-interior K] [--drop-unseen --datadir SCENE [--factor 4]] [--texture N [--texture-from render|dataset] --out mesh.obj]
-         [--report-error]
+         [--mesh-largest K] [--mesh-min-faces N] [--close-holes N] [--report-topology] [--report-error]
   python tools/extract_mesh.py --tsdf --fixture [--iters 1500] --out mesh.ply [--trunc T] [--view-step S] ...
   python tools/extract_mesh.py --tsdf CKPT.tar --datadir SCENE [--factor 4] --out mesh.ply [--trunc T] [--view-step S] ...
 
@@ -29,6 +29,15 @@ from --datadir / --factor.  Without the flag the file is what it was.
 csrc/mesh_raycast.hip) and writes only the faces that see past the mesh in at least one of them, on either side: interior
 shells go, exterior surface stays whether or not a camera saw it.  It needs no cameras; it comes after the clean-up and before
 --drop-unseen.  Without the flag the file is what it was.
+
+--mesh-largest K / --mesh-min-faces N keep the K largest connected components of the finished MESH, those of at least N faces
+(mesh.keep_components, csrc/mesh_topology.hip; faces joined by their edges): the islands that --drop-unseen and
+--drop-interior cut loose go, which the lattice options --keep-largest / --min-component cannot see.  --close-holes N then
+caps every closed boundary loop of at most N edges with a fan round its centroid (mesh.close_holes): right for the small
+cuts those options leave, wrong for large or bent holes, hence the limit.  --report-topology prints `topology: {JSON}` of the
+mesh that is written (mesh.topology: components, boundary / non-manifold / inconsistent edges, Euler characteristic, genus,
+loops).  They come after all other clean-up, in this order, and before --texture.  Without the flags every output is what
+it was.
 
 --report-error prints what the clean-up cost: the distance report of the finished mesh (after --smooth, --simplify and
 --drop-unseen) against the mesh as first extracted (evaluate.mesh_distance_metrics, csrc/mesh_distance.hip: Chamfer and sampled
@@ -150,6 +159,26 @@ def drop_unseen(a, m, hwf, poses):
     return out, t
 
 
+def mesh_topology_options(a, m):
+    """--mesh-largest / --mesh-min-faces, --close-holes, --report-topology on the finished Mesh m, in this order: (mesh, seconds)."""
+    t = 0.0
+    if a.mesh_largest is not None or a.mesh_min_faces is not None:
+        out, dt = _timed(lambda: mesh.keep_components(m, largest=a.mesh_largest, min_faces=a.mesh_min_faces))
+        print(f'mesh components kept: {m.faces.shape[0]} triangles, {m.verts.shape[0]} vertices -> {out.faces.shape[0]} triangles, '
+              f'{out.verts.shape[0]} vertices  ({dt * 1e3:.1f} ms)')
+        m, t = out, t + dt
+    if a.close_holes:
+        (out, capped, left), dt = _timed(lambda: mesh.close_holes(m, max_edges=a.close_holes))
+        print(f'holes of at most {a.close_holes} edges: {capped} capped, {left} loops left open, {m.faces.shape[0]} -> '
+              f'{out.faces.shape[0]} triangles  ({dt * 1e3:.1f} ms)')
+        m, t = out, t + dt
+    if a.report_topology:
+        rep = mesh.topology(m)
+        rep['per_component'] = rep['per_component'][:16]                     # the leading ones; `components` has the count
+        print('topology: ' + json.dumps(rep))
+    return m, t
+
+
 def view_images(a, te, hwf, poses, near, far, dataset):
     """--texture: uint8 images [V, H, W, 3] of the cameras poses: renders of the field, or dataset() with --texture-from dataset."""
     if a.texture_from == 'dataset':
@@ -232,6 +261,7 @@ def main_tsdf(ap, a, res, dev):
     m, t_clean = clean_up(a, first, lo32, hi32, res)
     m, _ = drop_interior(a, m)
     m, t_seen = drop_unseen(a, m, hwf, poses)
+    m, _ = mesh_topology_options(a, m)
     report_error(a, first, m, lo32, hi32, res)
     t_tex, t_ply = write_mesh(a, m, te, hwf, poses, near, far, dataset)
     print(f'tsdf zero level set: {m.verts.shape[0]} vertices, {m.faces.shape[0]} triangles -> {a.out}')
@@ -268,6 +298,11 @@ def main(argv=None):
                     help='bake a texture atlas of N texels per face leg from the training views and write OBJ + MTL + PNG (0: off)')
     ap.add_argument('--texture-from', choices=('render', 'dataset'), default='render',
                     help='--texture: the images are renders of the field at the training cameras, or the dataset\'s')
+    ap.add_argument('--mesh-largest', type=int, default=None, metavar='K', help='keep the K largest components of the finished mesh')
+    ap.add_argument('--mesh-min-faces', type=int, default=None, metavar='N', help='drop mesh components below N faces')
+    ap.add_argument('--close-holes', type=int, default=0, metavar='N',
+                    help='cap the closed boundary loops of at most N edges with a centroid fan (0: off)')
+    ap.add_argument('--report-topology', action='store_true', help='print the topology report of the mesh that is written')
     ap.add_argument('--report-error', action='store_true',
                     help='print the distance report of the finished mesh against the mesh as first extracted')
     ap.add_argument('--tsdf', action='store_true', help='fuse rendered depth maps instead of thresholding sigma')
@@ -290,6 +325,10 @@ def main(argv=None):
         ap.error('--smooth and --simplify must be >= 0')
     if not 0 <= a.drop_interior <= 255:
         ap.error('--drop-interior: 1..255 directions')
+    if (a.mesh_largest is not None and a.mesh_largest < 1) or (a.mesh_min_faces is not None and a.mesh_min_faces < 1):
+        ap.error('--mesh-largest and --mesh-min-faces must be >= 1')
+    if a.close_holes != 0 and a.close_holes < 3:
+        ap.error('--close-holes: at least 3 edges (0: off)')
     if not 0 <= a.texture <= 32 or (a.texture and not a.out.endswith('.obj')):
         ap.error('--texture: 1..32 texels, and --out must end in .obj')
     res = a.resolution[0] if len(a.resolution) == 1 else tuple(a.resolution)
@@ -337,6 +376,7 @@ def main(argv=None):
         near, far = float(bds.min() * .9), float(bds.max() * 1.)
     if a.drop_unseen:
         m, t_seen = drop_unseen(a, m, hwf, cam_poses)
+    m, _ = mesh_topology_options(a, m)
     report_error(a, first, m, a.bound_min, a.bound_max, res)
     t_tex, t_ply = write_mesh(a, m, kw, hwf, cam_poses, near, far, lambda: loaded[0])
     print(f'threshold {a.threshold}: {m.verts.shape[0]} vertices, {m.faces.shape[0]} triangles -> {a.out}')
