@@ -1254,6 +1254,34 @@ int mvip_mesh_topology_cap_emit(const float *verts, const void *colors, const in
                                 const int *loop_offsets, const int *loop_items, int64_t n_caps, int64_t n_cap_faces,
                                 float *new_verts, void *new_colors, int *new_faces, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mesh voxelisation: an indexed triangle mesh as a bit grid in the convention of the occupancy / region grids above, as the
+ * cells its faces touch (conservative) and as the cells inside it (column parity from up to three axes with a majority vote)
+ * (beyond the reference, which has no mesh export: no entry point has a reference call site; csrc/mesh_voxel.hip,
+ * ops.mesh_voxelize_surface / mesh_voxelize_solid, mesh.voxelize, Region.from_mesh, OccupancyGrid.from_mesh).  The
+ * definitions -- lattice coordinates, the snapped integer coverage with its ownership rule, the crossing cell, the exact
+ * triangle-box overlap with its margin -- are written out in csrc/mesh_voxel.hip and tests/voxel_numpy.py; everything is
+ * fp64 and integers, every mark an integer OR / XOR: the result does not depend on the order of the atomics.
+ * box = (bmin[3], inv[3]) and cells[3] in HOST memory as for the grids above; words [(cx cy cz + 31) / 32] int32.
+ * axes: 0, 1, 2 = the column axis x, y, z alone, 3 = all three with the majority.  counters [5] int32 (DEVICE): [0] a flag,
+ * non-zero when a face index lies outside [0, Nv) (that face is dropped), [1] the dropped faces, [2..4] the columns of odd
+ * total parity per axis (0 for an axis not walked); mvip_voxel_surface and mvip_voxel_crossings clear all five.
+ * scratch: mvip_voxel_scratch_words(cells, axes) int32 words (-1 for bad arguments), the crossing grids of the walked axes:
+ * per axis [cx, cy, (cz + 31) / 32] words, bit iz & 31 of word iz >> 5 of row (ix, iy).
+ * Every launch on the caller's stream.  MVIP_EINVAL before any device call for: a NULL operand (verts / faces only where
+ * their count is non-zero), a negative count, Nv or 3 F > 2^31 - 1, cells outside 1..512, a non-finite or non-positive inv, a
+ * non-finite bmin, axes outside 0..3.  F = 0 and Nv = 0 are valid and give an all-clear grid.
+ * mvip_voxel_surface: clears words and counters, then one thread per face ORs the cells the face overlaps into words.
+ * mvip_voxel_crossings: clears scratch and counters, then one thread per (face, walked axis) XORs the crossing bits.
+ * mvip_voxel_fill: the prefix parity of scratch along each walked axis in place (counters [2..4] receive the odd columns),
+ *   then one thread per word of words writes the single axis or the majority. */
+int64_t mvip_voxel_scratch_words(const int *cells, int axes);
+int mvip_voxel_surface(const float *verts, const int *faces, int64_t n_verts, int64_t n_faces, const float *box,
+                       const int *cells, int *words, int *counters, void *stream);
+int mvip_voxel_crossings(const float *verts, const int *faces, int64_t n_verts, int64_t n_faces, const float *box,
+                         const int *cells, int axes, int *scratch, int *counters, void *stream);
+int mvip_voxel_fill(int *scratch, const int *cells, int axes, int *words, int *counters, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

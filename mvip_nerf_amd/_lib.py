@@ -251,6 +251,10 @@ _SIGNATURES = {
     'mvip_mesh_topology_loops_emit': (_int, [_i64, _c_f, _c_f, _c_f, _i64] + [_c_f] * 5),
     'mvip_mesh_topology_cap_plan': (_int, [_i64, _c_f, _i64, _c_f, _c_f, _i64] + [_c_f] * 8),
     'mvip_mesh_topology_cap_emit': (_int, [_c_f, _c_f, _c_f, _i64, _i64, _i64] + [_c_f] * 6 + [_i64, _i64] + [_c_f] * 4),
+    'mvip_voxel_scratch_words': (_i64, [ctypes.POINTER(_int), _int]),
+    'mvip_voxel_surface': (_int, [_c_f, _c_f, _i64, _i64, ctypes.POINTER(_flt), ctypes.POINTER(_int), _c_f, _c_f, _c_f]),
+    'mvip_voxel_crossings': (_int, [_c_f, _c_f, _i64, _i64, ctypes.POINTER(_flt), ctypes.POINTER(_int), _int, _c_f, _c_f, _c_f]),
+    'mvip_voxel_fill': (_int, [_c_f, ctypes.POINTER(_int), _int, _c_f, _c_f, _c_f]),
 }
 
 # every symbol include/mvip_nerf.h declares; tests check the built library exports all of them

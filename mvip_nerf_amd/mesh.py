@@ -755,6 +755,41 @@ def keep_components(mesh, largest=None, min_faces=None, containing=None, connect
     return keep_faces(mesh, torch.from_numpy(keep).to(mesh.faces.device)[labels.to(torch.int64)].bool())
 
 
+VOXEL_MODES = ('surface', 'solid', 'both')
+
+
+def voxelize(mesh, bmin, bmax, cells, mode='both', axes='majority'):
+    """(grid, report): `mesh` as a bitgrid.BitGrid on the box [bmin, bmax] cut into `cells` (ops.mesh_voxelize_surface /
+    mesh_voxelize_solid, csrc/mesh_voxel.hip).  mode 'surface': the cells the faces touch, conservatively (every point of a face
+    that the renderer's cell lookup places in the box lies in a set cell); 'solid': the cells whose centres are inside, by column
+    parity along `axes` ('x', 'y', 'z', or 'majority' of the three -- the one to use on meshes with holes, such as TSDF meshes);
+    'both': the OR of the two.  report: a dict of `dropped` (faces left out: non-finite or, for 'solid', beyond the guard band;
+    the larger of the two counts under 'both'), `odd_columns` (three integers, the leak diagnostic of 'solid': columns of odd
+    parity per axis -- zero for a closed mesh that no column ends inside; None for 'surface'), `count` (set cells), `volume`
+    (count x the volume of a cell) and `cells`.  The grid is a plain BitGrid: Region.from_mesh and OccupancyGrid.from_mesh give
+    it a meaning."""
+    from . import bitgrid
+    if mode not in VOXEL_MODES:
+        raise ValueError(f'voxelize: mode must be one of {VOXEL_MODES}, got {mode!r}')
+    if axes not in ops.VOXEL_AXES:
+        raise ValueError(f'voxelize: axes must be one of {ops.VOXEL_AXES}, got {axes!r}')
+    dev = mesh.verts.device
+    cells = bitgrid._cells(cells)
+    grid = bitgrid.BitGrid(bmin, bmax, cells, torch.zeros(ops.occupancy_words(cells), device=dev, dtype=torch.int32))
+    words, dropped, odd = None, 0, None
+    if mode in ('surface', 'both'):
+        words, dropped = ops.mesh_voxelize_surface(mesh.verts, mesh.faces, grid.box(), cells)
+    if mode in ('solid', 'both'):
+        w, odd, d = ops.mesh_voxelize_solid(mesh.verts, mesh.faces, grid.box(), cells, axes)
+        words = w if words is None else words | w
+        dropped = max(dropped, d)
+    grid = bitgrid.BitGrid(grid.bmin, grid.bmax, cells, words)
+    count = grid.count()
+    cell_volume = float(np.prod((grid.bmax.astype(np.float64) - grid.bmin.astype(np.float64)) / np.asarray(cells, np.float64)))
+    return grid, {'dropped': int(dropped), 'odd_columns': None if odd is None else [int(o) for o in odd], 'count': count,
+                  'volume': count * cell_volume, 'cells': cells}
+
+
 def boundary_loops(mesh):
     """ops.MeshBoundaryLoops(loop_of [3F], next [3F], first [L], sizes [L], closed [L]) of the mesh's boundary: the holes of a
     surface that should be closed, the rim of one that is a sheet.  See ops.mesh_boundary_loops."""

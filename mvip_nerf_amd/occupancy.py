@@ -78,6 +78,22 @@ class OccupancyGrid(BitGrid):
         return cls(lo, hi, cells, words)
 
     @classmethod
+    def from_mesh(cls, mesh, bmin, bmax, cells=128, solid=True, dilate=1):
+        """The cells of a mesh.Mesh on the GPU as occupied cells (mesh.voxelize, csrc/mesh_voxel.hip), then `dilate` rounds
+        of dilation: the cells the faces touch, and with solid=True the cells inside as well (column parity, the majority of
+        three axes).  Like keep_components, and unlike from_model, this grid is NOT conservative for the field: a render with
+        it shows the scene ONLY where the mesh is -- whatever the cleaned mesh no longer has (floaters, dropped interior,
+        deselected components) is gone from the frame, not merely skipped, so the frame differs from the unskipped render."""
+        cells = _cells(cells)
+        rounds = _count('dilate', dilate, 0, MAX_CELLS_PER_AXIS)
+        from .mesh import voxelize                                   # (the argument shadows the module here)
+        grid, _ = voxelize(mesh, bmin, bmax, cells, mode='both' if solid else 'surface')
+        words = grid.words
+        for _ in range(rounds):
+            words = ops.occupancy_dilate(words, cells)
+        return cls(grid.bmin, grid.bmax, cells, words)
+
+    @classmethod
     def from_model(cls, render_kwargs, bmin, bmax, cells=128, threshold=DEFAULT_THRESHOLD, samples_per_cell=2, dilate=1,
                    networks=('coarse', 'fine'), chunk=1 << 18):
         """mesh.density_grid per network of `networks` at cells * samples_per_cell + 1 points per axis, from_density of

@@ -3573,3 +3573,85 @@ def mesh_texture_resolve(face, verts, faces, atlas, texels, poses, focal, near=1
          ptr(a, torch.uint8) if F else none, int(texels), ptr(p) if V else none, V, H, W, focal, near,
          ptr(rgb, torch.uint8) if V else none, stream())
     return rgb
+
+
+# mesh voxelisation: the cells a mesh's faces touch and the cells inside it, as bit-grid words (beyond the reference,
+# csrc/mesh_voxel.hip) ---------------------------------------------------------------------------------------------------------
+# The definitions are csrc/mesh_voxel.hip's and tests/voxel_numpy.py's.  There is no CPU path.
+
+VOXEL_AXES = ('x', 'y', 'z', 'majority')
+VOXEL_COUNTERS = 5                 # flag, dropped, odd columns x / y / z (csrc/mesh_voxel.hip: N_COUNTERS)
+
+
+def _voxel_args(what, verts, faces, box, cells):
+    import ctypes
+    import math
+    import numpy as np
+    v, f = _mesh_operands(what, verts, faces)
+    try:
+        box = [float(b) for b in box]
+        cells = [int(c) for c in cells]
+    except (TypeError, ValueError):
+        raise ValueError(f'{what}: box must be six numbers (bmin, inv) and cells three integers') from None
+    if len(box) != 6 or len(cells) != 3 or not all(1 <= c <= 512 for c in cells):
+        raise ValueError(f'{what}: box must be six numbers (bmin, inv) and cells three integers in 1..512, got {box} and {cells}')
+    with np.errstate(over='ignore'):
+        box32 = [float(np.float32(b)) for b in box]
+    if not all(math.isfinite(b) for b in box32) or not all(b > 0 for b in box32[3:]):
+        raise ValueError(f'{what}: box {box}: bmin must be finite and inv finite and > 0 in fp32')
+    return v, f, (ctypes.c_float * 6)(*box32), (ctypes.c_int * 3)(*cells), tuple(cells)
+
+
+def mesh_voxelize_surface(verts, faces, box, cells):
+    """(words, dropped): the cells of a bit grid that the faces of an indexed mesh touch, conservatively.  verts [Nv, 3] fp32 and
+    faces [F, 3] int32 on the GPU; box = (bmin[3], inv[3]) as BitGrid.box() gives it and cells three integers in 1..512 (host).
+    words: int32 [(cx cy cz + 31) // 32] in the layout of bitgrid.py.  A cell is set iff some face overlaps the cell grown by
+    2^-12 of a cell on every side (the exact triangle-box test in fp64, csrc/mesh_voxel.hip), so every fp32 point of a face that
+    the renderer's own cell lookup places in the box lies in a set cell.  dropped: the number of faces with a non-finite vertex
+    (they mark nothing).  F = 0 and Nv = 0 give a clear grid.  ValueError for bad shapes or dtypes, CPU tensors, a bad box or
+    cells, or a face index outside [0, Nv) (checked on the device; the counters are read back once: the only synchronisation).
+    Integer OR marks: a call equals its repetition bit for bit.  Detached."""
+    what = 'mesh_voxelize_surface'
+    v, f, cbox, ccells, cells = _voxel_args(what, verts, faces, box, cells)
+    Nv, F = int(v.shape[0]), int(f.shape[0])
+    words = torch.empty(occupancy_words(cells), device=v.device, dtype=_I32)
+    counters = torch.empty(VOXEL_COUNTERS, device=v.device, dtype=_I32)
+    none = ptr(None)
+    call('mvip_voxel_surface', ptr(v) if Nv else none, ptr(f, _I32) if F else none, Nv, F, cbox, ccells, ptr(words, _I32),
+         ptr(counters, _I32), stream())
+    c = counters.cpu().tolist()
+    if c[0]:
+        raise ValueError(f'{what}: a face index lies outside [0, {Nv})')
+    return words, c[1]
+
+
+def mesh_voxelize_solid(verts, faces, box, cells, axes='majority'):
+    """(words, odd_columns, dropped): the cells of a bit grid whose centres lie inside an indexed mesh, by the parity of the
+    crossings of the cell columns along `axes`: 'x', 'y' or 'z' alone, or 'majority' -- all three, a cell set iff at least two
+    agree (operands as mesh_voxelize_surface).  Vertices are snapped to 8 sub-cell bits and coverage is decided in integers with
+    the rasteriser's ownership rule (csrc/mesh_voxel.hip): for a closed mesh every column is even and a centre farther than 2^-8
+    of a cell from the surface gets the exact answer; a hole leaks whole column segments on a single axis, and under 'majority'
+    changes nothing outside the missing faces' bounding boxes.  odd_columns: a list of three integers, the columns of odd total
+    parity per axis (0 for an axis not walked) -- the leak diagnostic.  dropped: the faces left out whole because a vertex is
+    not finite or lies more than 16,384 cells from the box origin on a rastered axis.  ValueError as mesh_voxelize_surface, and
+    for an unknown `axes`.  Integer XOR marks: a call equals its repetition bit for bit.  Detached."""
+    what = 'mesh_voxelize_solid'
+    v, f, cbox, ccells, cells = _voxel_args(what, verts, faces, box, cells)
+    if axes not in VOXEL_AXES:
+        raise ValueError(f'{what}: axes must be one of {VOXEL_AXES}, got {axes!r}')
+    a = VOXEL_AXES.index(axes)
+    Nv, F = int(v.shape[0]), int(f.shape[0])
+    n_scratch = _lib.load().mvip_voxel_scratch_words(ccells, a)
+    if n_scratch < 0:
+        raise _lib.MvipError(f'{what}: no scratch size for cells {cells}')
+    scratch = torch.empty(n_scratch, device=v.device, dtype=_I32)
+    words = torch.empty(occupancy_words(cells), device=v.device, dtype=_I32)
+    counters = torch.empty(VOXEL_COUNTERS, device=v.device, dtype=_I32)
+    none = ptr(None)
+    call('mvip_voxel_crossings', ptr(v) if Nv else none, ptr(f, _I32) if F else none, Nv, F, cbox, ccells, a, ptr(scratch, _I32),
+         ptr(counters, _I32), stream())
+    call('mvip_voxel_fill', ptr(scratch, _I32), ccells, a, ptr(words, _I32), ptr(counters, _I32), stream())
+    c = counters.cpu().tolist()
+    if c[0]:
+        raise ValueError(f'{what}: a face index lies outside [0, {Nv})')
+    return words, c[2:5], c[1]

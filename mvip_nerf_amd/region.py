@@ -116,6 +116,28 @@ class Region(BitGrid):
         return r.dilate(rounds)
 
     @classmethod
+    def from_mesh(cls, mesh, bmin=None, bmax=None, cells=64, solid=True, dilate=1):
+        """The cells of a mesh (mesh.voxelize, csrc/mesh_voxel.hip), then `dilate` rounds of dilation: with solid=True the
+        cells the faces touch and the cells inside (column parity, the majority of three axes: a hole in the mesh leaks
+        nothing beyond the missing faces' own cells), with solid=False the surface cells only.  mesh: a mesh.Mesh on the
+        GPU, for instance one component picked by mesh.keep_components(containing=...).  With no box given: default_box over
+        the finite vertices, as from_points.  The region renders into every view as an occlusion-aware mask (propagate_masks)
+        and carve() cuts it out of the scene."""
+        cells = _cells(cells)
+        rounds = _count('dilate', dilate, 0, MAX_CELLS_PER_AXIS)
+        if (bmin is None) != (bmax is None):
+            raise ValueError('give both bmin and bmax, or neither')
+        if bmin is None:
+            v = mesh.verts.detach().reshape(-1, 3)
+            finite = v[torch.isfinite(v).all(-1)]
+            if finite.shape[0] == 0:
+                raise ValueError('no finite vertex: the box cannot be derived from the mesh')
+            bmin, bmax = default_box(finite.min(0).values.cpu().numpy(), finite.max(0).values.cpu().numpy(), cells, rounds)
+        from .mesh import voxelize                                   # (the argument shadows the module here)
+        grid, _ = voxelize(mesh, bmin, bmax, cells, mode='both' if solid else 'surface')
+        return cls(grid.bmin, grid.bmax, cells, grid.words).dilate(rounds)
+
+    @classmethod
     def from_masks(cls, render_kwargs, hwf, poses, masks, near, far, bmin=None, bmax=None, cells=64, min_weight=None,
                    dilate=1, chunk=1 << 15):
         """Lift masks [V, H, W] (bool; poses [V, 3, 4] camera-to-world) into a region.  Per annotated view, under

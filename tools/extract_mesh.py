@@ -7,6 +7,7 @@ binary PLY (mvip_nerf_amd/mesh.py).  Prints sigma percentiles of the grid (to ch
          [--keep-largest K] [--min-component N] [--smooth ITERS] [--simplify STEPS] [--simplify-placement quadric|mean]
          [--drop-interior K] [--drop-unseen --datadir SCENE [--factor 4]] [--texture N [--texture-from render|dataset] --out mesh.obj]
          [--mesh-largest K] [--mesh-min-faces N] [--close-holes N] [--report-topology] [--report-error]
+         [--save-region R.npz] [--save-occupancy O.npz] [--grid-cells 128] [--grid-dilate 1]
   python tools/extract_mesh.py --tsdf --fixture [--iters 1500] --out mesh.ply [--trunc T] [--view-step S] ...
   python tools/extract_mesh.py --tsdf CKPT.tar --datadir SCENE [--factor 4] --out mesh.ply [--trunc T] [--view-step S] ...
 
@@ -51,6 +52,13 @@ csrc/texture.hip) and writes Wavefront OBJ + MTL + PNG; --out must end in .obj. 
 (--texture-from render, the default) or the loader's images (--texture-from dataset); the cameras are those of --tsdf, else
 --datadir / --factor.  Texels that no view sees are filled from the field (the head-on query of the vertex colours).  --out
 *.obj without --texture writes the OBJ alone, with no texture coordinates.  Without the two flags every output is what it was.
+
+--save-region PATH / --save-occupancy PATH voxelise the mesh that is written (mesh.voxelize, csrc/mesh_voxel.hip: the cells its
+faces touch and the cells inside, by column parity with a majority of three axes) on the extraction box at --grid-cells cells
+per axis, dilated --grid-dilate rounds, and save it as a region (Region.from_mesh: the masks of the object in every view, and
+its carve) or as an occupancy grid (OccupancyGrid.from_mesh: a render with it shows the scene ONLY where the mesh is).  The
+set cells, the dropped faces and the odd columns (the leak diagnostic) are printed.  Without the flags every output is what it
+was.
 
 --tsdf meshes what the renderer sees instead of thresholding sigma (mesh.fuse_depths): the disparity of every view (every
 S-th with --view-step S) is rendered and fused into a truncated signed distance field whose zero level set is extracted
@@ -179,6 +187,22 @@ def mesh_topology_options(a, m):
     return m, t
 
 
+def save_grids(a, m, lo, hi):
+    """--save-region / --save-occupancy: the grids of the finished Mesh m on the box [lo, hi]."""
+    if not a.save_region and not a.save_occupancy:
+        return
+    from mvip_nerf_amd.occupancy import OccupancyGrid
+    from mvip_nerf_amd.region import Region
+    (_, rep), t = _timed(lambda: mesh.voxelize(m, lo, hi, a.grid_cells))
+    print(f'voxels at {a.grid_cells} cells per axis: {rep["count"]} set ({rep["volume"]:.6g} world units^3), {rep["dropped"]} faces dropped, '
+          f'odd columns {rep["odd_columns"]}  ({t * 1e3:.1f} ms)')
+    for path, cls in ((a.save_region, Region), (a.save_occupancy, OccupancyGrid)):
+        if path:
+            g = cls.from_mesh(m, lo, hi, cells=a.grid_cells, dilate=a.grid_dilate)
+            g.save(path)
+            print(f'{cls.NOUN}: {g.count()} of {g.n_cells} cells after {a.grid_dilate} rounds of dilation -> {path}')
+
+
 def view_images(a, te, hwf, poses, near, far, dataset):
     """--texture: uint8 images [V, H, W, 3] of the cameras poses: renders of the field, or dataset() with --texture-from dataset."""
     if a.texture_from == 'dataset':
@@ -263,6 +287,7 @@ def main_tsdf(ap, a, res, dev):
     m, t_seen = drop_unseen(a, m, hwf, poses)
     m, _ = mesh_topology_options(a, m)
     report_error(a, first, m, lo32, hi32, res)
+    save_grids(a, m, lo32, hi32)
     t_tex, t_ply = write_mesh(a, m, te, hwf, poses, near, far, dataset)
     print(f'tsdf zero level set: {m.verts.shape[0]} vertices, {m.faces.shape[0]} triangles -> {a.out}')
     print(f'time  model {t_model * 1e3:.1f} ms  render {t_render * 1e3:.1f} ms  fusion {t_fuse * 1e3:.1f} ms  components {t_cc * 1e3:.1f} ms  '
@@ -305,6 +330,10 @@ def main(argv=None):
     ap.add_argument('--report-topology', action='store_true', help='print the topology report of the mesh that is written')
     ap.add_argument('--report-error', action='store_true',
                     help='print the distance report of the finished mesh against the mesh as first extracted')
+    ap.add_argument('--save-region', metavar='PATH', help='save the written mesh as a region (.npz)')
+    ap.add_argument('--save-occupancy', metavar='PATH', help='save the written mesh as an occupancy grid (.npz)')
+    ap.add_argument('--grid-cells', type=int, default=128, metavar='N', help='cells per axis of the saved grids')
+    ap.add_argument('--grid-dilate', type=int, default=1, metavar='R', help='dilation rounds of the saved grids')
     ap.add_argument('--tsdf', action='store_true', help='fuse rendered depth maps instead of thresholding sigma')
     ap.add_argument('--fixture', action='store_true', help='--tsdf: train the scene-1 fixture and use its cameras')
     ap.add_argument('--iters', type=int, default=1500, help='training iterations of --fixture')
@@ -331,6 +360,8 @@ def main(argv=None):
         ap.error('--close-holes: at least 3 edges (0: off)')
     if not 0 <= a.texture <= 32 or (a.texture and not a.out.endswith('.obj')):
         ap.error('--texture: 1..32 texels, and --out must end in .obj')
+    if not 1 <= a.grid_cells <= 512 or not 0 <= a.grid_dilate <= 512:
+        ap.error('--grid-cells: 1..512, --grid-dilate: 0..512')
     res = a.resolution[0] if len(a.resolution) == 1 else tuple(a.resolution)
     dev = torch.device('cuda', 0)
     if a.tsdf:
@@ -378,6 +409,7 @@ def main(argv=None):
         m, t_seen = drop_unseen(a, m, hwf, cam_poses)
     m, _ = mesh_topology_options(a, m)
     report_error(a, first, m, a.bound_min, a.bound_max, res)
+    save_grids(a, m, a.bound_min, a.bound_max)
     t_tex, t_ply = write_mesh(a, m, kw, hwf, cam_poses, near, far, lambda: loaded[0])
     print(f'threshold {a.threshold}: {m.verts.shape[0]} vertices, {m.faces.shape[0]} triangles -> {a.out}')
     print(f'time  density grid {t_grid * 1e3:.1f} ms  components {t_cc * 1e3:.1f} ms  marching cubes {t_mc * 1e3:.1f} ms  colours {t_col * 1e3:.1f} ms  '

@@ -3,6 +3,7 @@ into a region through the trained field's ray weights, render the region into ev
 
   python tools/propagate_masks.py --fixture [--views 0,15,29] [--views 0 ...] --out DIR
   python tools/propagate_masks.py --checkpoint CKPT.tar --datadir SCENE [--factor 4] --views 0,15,29 --out DIR
+  python tools/propagate_masks.py (--fixture | --checkpoint ... --datadir ...) --mesh A.ply [--mesh-point X,Y,Z] --out DIR
 
 --fixture trains the scene-1 fixture (tests/golden/scene1_small.npz, the 1,500-iteration recipe of
 tools/render_occupancy_ab.py::train_scene1) and annotates with the fixture's own masks; --checkpoint / --datadir load a
@@ -10,6 +11,11 @@ model in the reference's .tar format and a SPIn-NeRF style scene, and annotate w
 named.  --views may be repeated: one run per annotated set, the field trained or loaded once.  --keep-largest K keeps
 only the K largest connected components of the lifted region (BitGrid.keep_components, connectivity 6) before it is
 propagated; the JSON then carries the cell and component counts before the cut as well.
+
+--mesh A.ply builds the region from a mesh instead of from annotated views (Region.from_mesh, csrc/mesh_voxel.hip: the cells
+the mesh touches and the cells inside it; --cells and --dilate as for the lifted region): the whole mesh, or with --mesh-point
+X,Y,Z the connected component whose surface is closest to that point (mesh.keep_components).  No view is annotated: the IoU is
+reported over every view that has a dataset mask, there is no copy baseline, and the set's folder is DIR/mesh/.
 
 Per set, into DIR/views_<set>/: label/NNNNNN.png (0 / 255, one per view, the layout load_llff._load_data reads; with
 --datadir the scene's own file names), region.npz (Region.save), with --carve-preview VIEW that view rendered with and
@@ -30,7 +36,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-from mvip_nerf_amd import run                                                # noqa: E402
+from mvip_nerf_amd import mesh, run                                          # noqa: E402
 from mvip_nerf_amd.region import Region, propagate_masks                     # noqa: E402
 from mvip_nerf_amd.run_nerf_helpers import to8b                              # noqa: E402
 
@@ -77,6 +83,17 @@ def checkpoint_scene(device, ckpt, datadir, factor):
         {'checkpoint': ckpt, 'step': step, 'datadir': datadir, 'factor': factor}
 
 
+def region_from_mesh(a, device):
+    """--mesh: the region of the PLY's mesh, or of the component closest to --mesh-point."""
+    m = mesh.load_ply(a.mesh, device)
+    if a.mesh_point:
+        point = [float(v) for v in a.mesh_point.split(',')]
+        if len(point) != 3:
+            raise SystemExit('--mesh-point: X,Y,Z')
+        m = mesh.keep_components(m, containing=torch.tensor([point]))
+    return Region.from_mesh(m, cells=a.cells, dilate=a.dilate)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('--fixture', action='store_true')
@@ -91,10 +108,14 @@ def main(argv=None):
     ap.add_argument('--min-weight', type=float, default=None)
     ap.add_argument('--threshold', type=float, default=0.5)
     ap.add_argument('--keep-largest', type=int, default=None, metavar='K', help='keep the K largest components of the region')
+    ap.add_argument('--mesh', metavar='PLY', help='build the region from this mesh instead of from annotated views')
+    ap.add_argument('--mesh-point', metavar='X,Y,Z', help='--mesh: only the component closest to this point')
     ap.add_argument('--carve-preview', type=int, default=None, metavar='VIEW')
     a = ap.parse_args(argv)
     if a.fixture == bool(a.checkpoint) or bool(a.checkpoint) != bool(a.datadir):
         ap.error('either --fixture, or --checkpoint with --datadir')
+    if (a.mesh_point and not a.mesh) or (a.mesh and a.views):
+        ap.error('--mesh-point belongs to --mesh; --mesh and --views exclude each other')
     dev = torch.device('cuda', 0)
 
     def timed(fn):
@@ -111,15 +132,18 @@ def main(argv=None):
            'settings': {'cells': a.cells, 'dilate': a.dilate, 'min_weight': a.min_weight or 'default 1 / S', 'threshold': a.threshold},
            'seconds_model': t_model, 'sets': []}
     os.makedirs(a.out, exist_ok=True)
-    for spec in (a.views or ['0,15,29']):
-        annotated = [int(v) for v in spec.split(',')]
+    for spec in ([None] if a.mesh else (a.views or ['0,15,29'])):
+        annotated = [] if spec is None else [int(v) for v in spec.split(',')]
         missing = [v for v in annotated if not valid[v]]
         if missing:
             raise SystemExit(f'views {missing} have no mask to annotate with')
-        folder = os.path.join(a.out, 'views_' + '_'.join(str(v) for v in annotated))
+        folder = os.path.join(a.out, 'mesh' if spec is None else 'views_' + '_'.join(str(v) for v in annotated))
         os.makedirs(os.path.join(folder, 'label'), exist_ok=True)
-        region, t_lift = timed(lambda: Region.from_masks(te, hwf, poses[annotated], torch.from_numpy(masks[annotated]).to(dev),
-                                                         near, far, cells=a.cells, min_weight=a.min_weight, dilate=a.dilate))
+        if spec is None:
+            region, t_lift = timed(lambda: region_from_mesh(a, dev))
+        else:
+            region, t_lift = timed(lambda: Region.from_masks(te, hwf, poses[annotated], torch.from_numpy(masks[annotated]).to(dev),
+                                                             near, far, cells=a.cells, min_weight=a.min_weight, dilate=a.dilate))
         lifted = None
         if a.keep_largest is not None:
             lifted = {'region_cells_lifted': region.count(), 'region_components_lifted': int(region.components()[1].shape[0]),
@@ -132,15 +156,19 @@ def main(argv=None):
             run._write_png(os.path.join(folder, 'label', name + '.png'), np.repeat(hard[v][..., None].astype(np.uint8) * 255, 3, -1))
         ious = {v: iou(hard[v], masks[v]) for v in range(len(masks)) if valid[v]}
         others = [v for v in ious if v not in annotated]
-        base = copy_baseline(masks, poses_np, annotated, valid)
+        base = copy_baseline(masks, poses_np, annotated, valid) if annotated else {}
+        mean_of = lambda values: float(np.mean(values)) if len(values) else None
+        min_of = lambda values: float(np.min(values)) if len(values) else None
         rec = {'annotated': annotated, 'region_cells': region.count(), 'region_share_of_box': region.fraction(),
                'box_min': [float(v) for v in region.bmin], 'box_max': [float(v) for v in region.bmax],
                'iou_per_view': {str(v): ious[v] for v in ious}, 'copy_baseline_per_view': {str(v): base[v] for v in base},
-               'mean_iou_other_views': float(np.mean([ious[v] for v in others])), 'min_iou_other_views': float(np.min([ious[v] for v in others])),
-               'copy_baseline_mean': float(np.mean(list(base.values()))), 'copy_baseline_min': float(np.min(list(base.values()))),
-               'mean_iou_annotated_views': float(np.mean([ious[v] for v in annotated])),
+               'mean_iou_other_views': mean_of([ious[v] for v in others]), 'min_iou_other_views': min_of([ious[v] for v in others]),
+               'copy_baseline_mean': mean_of(list(base.values())), 'copy_baseline_min': min_of(list(base.values())),
+               'mean_iou_annotated_views': mean_of([ious[v] for v in annotated]),
                'seconds_lift': t_lift, 'seconds_propagate_all_views': t_prop}
         rec.update(lifted or {})
+        if spec is None:
+            rec.update(mesh=a.mesh, mesh_point=a.mesh_point)
         if a.carve_preview is not None:
             with torch.no_grad():
                 kw = dict(te, near=near, far=far)
