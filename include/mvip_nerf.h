@@ -1282,6 +1282,36 @@ int mvip_voxel_crossings(const float *verts, const int *faces, int64_t n_verts, 
                          const int *cells, int axes, int *scratch, int *counters, void *stream);
 int mvip_voxel_fill(int *scratch, const int *cells, int axes, int *words, int *counters, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Signed mesh distance: the closest point of mvip_mesh_distance_query with a sign from the angle-weighted pseudonormal of the
+ * closest feature (Baerentzen and Aanaes 2005), for N points or for the points of a lattice generated in the kernel (beyond
+ * the reference, which has no mesh export: no entry point has a reference call site; csrc/mesh_sdf.hip,
+ * ops.mesh_vertex_pseudonormals / mesh_signed_distance / mesh_signed_distance_lattice, mesh.signed_distance / sdf_grid /
+ * remesh, the `margin` of Region.from_mesh / OccupancyGrid.from_mesh).  The definition -- the feature code, the three
+ * pseudonormals, the sign, the band, the lattice coordinates -- is written out in csrc/mesh_sdf.hip and
+ * tests/mesh_sdf_numpy.py; the result does not depend on the grid.  The mesh and its face grid are the operands of
+ * mvip_mesh_distance_query.  One launch each on the caller's stream, one thread per vertex / per query, no atomics:
+ * bit-reproducible given pseudonormals.  MVIP_EINVAL before any device call for: a count < 0, V, 3 F, N or the pair count
+ * > 2^31 - 1, F = 0 (V = 0) in the query, a bad box / cells, max_dist NaN or < 0, a lattice with a count < 1, a non-finite
+ * lo or a step that is not finite and > 0, `point` given with 3 N > 2^31 - 1, a NULL operand that a non-zero count makes
+ * necessary.  N = 0 is valid.
+ * mvip_mesh_vertex_pseudonormals: offsets [V+1] / corners [3F]: the corner table of mvip_mesh_corner_table over faces.
+ *   pseudonormals [V,3] fp64 = per vertex the sum, in list order, of angle x unit face normal over its corners (unnormalised;
+ *   zeros for a vertex without a corner; a corner of a face with an index outside [0, V) adds nothing).  F = 0 is valid.
+ * mvip_mesh_signed_distance: points [N,3] fp32, or NULL with lattice_lo[3], lattice_h[3] (fp32) and lattice_counts[3] in HOST
+ *   memory: then N must be their product and point (i, j, k), k fastest, is fp32(fp32(i) h) + lo per axis.  twin [3F] of
+ *   mvip_mesh_topology_edges_find; pseudonormals [V,3] fp64.  max_dist: the band B (+inf: none).  sdist [N] fp32 (negative
+ *   inside a closed, outward-oriented mesh), face [N]; point [N,3] and feature [N] (0 interior, 1..3 edge ab / bc / ca, 4..6
+ *   vertex a / b / c of `face`) or NULL.  A query with a NaN or infinite coordinate, or farther than B: face -1, feature -1,
+ *   sdist and point NaN.  stats: NULL, or two 64-bit words as for mvip_mesh_distance_query (a counting variant of the kernel). */
+int mvip_mesh_vertex_pseudonormals(const float *verts, const int *faces, int64_t n_verts, int64_t n_faces, const int *offsets,
+                                   const int *corners, double *pseudonormals, void *stream);
+int mvip_mesh_signed_distance(const float *points, const float *lattice_lo, const float *lattice_h, const int *lattice_counts,
+                              int64_t n_points, const float *verts, const int *faces, int64_t n_verts, int64_t n_faces,
+                              const float *box, const int *cells, const int *cell_offsets, const int *cell_faces,
+                              int64_t n_pairs, const int *twin, const double *pseudonormals, double max_dist, float *sdist,
+                              int *face, float *point, int *feature, void *stats, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

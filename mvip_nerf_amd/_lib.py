@@ -255,6 +255,10 @@ _SIGNATURES = {
     'mvip_voxel_surface': (_int, [_c_f, _c_f, _i64, _i64, ctypes.POINTER(_flt), ctypes.POINTER(_int), _c_f, _c_f, _c_f]),
     'mvip_voxel_crossings': (_int, [_c_f, _c_f, _i64, _i64, ctypes.POINTER(_flt), ctypes.POINTER(_int), _int, _c_f, _c_f, _c_f]),
     'mvip_voxel_fill': (_int, [_c_f, ctypes.POINTER(_int), _int, _c_f, _c_f, _c_f]),
+    'mvip_mesh_vertex_pseudonormals': (_int, [_c_f, _c_f, _i64, _i64, _c_f, _c_f, _c_f, _c_f]),
+    'mvip_mesh_signed_distance': (_int, [_c_f, ctypes.POINTER(_flt), ctypes.POINTER(_flt), ctypes.POINTER(_int), _i64, _c_f, _c_f, _i64,
+                                         _i64, ctypes.POINTER(_flt), ctypes.POINTER(_int), _c_f, _c_f, _i64, _c_f, _c_f,
+                                         ctypes.c_double, _c_f, _c_f, _c_f, _c_f, _c_f, _c_f]),
 }
 
 # every symbol include/mvip_nerf.h declares; tests check the built library exports all of them

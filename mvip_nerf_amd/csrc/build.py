@@ -24,7 +24,7 @@ LIB_PATH = os.path.join(LIB_DIR, 'libmvipnerf.so')
 SOURCES = ['api.hip', 'rays.hip', 'composite.hip', 'sample_pdf.hip', 'mlp_pack.hip', 'mlp_fwd.hip', 'mlp_fwd16.hip', 'mlp_fwd16_fold.hip', 'mlp_encode16_probe.hip', 'mlp_fwd_f16x3.hip', 'mlp_fwd16_f16x3.hip',
            'mlp_bwd.hip', 'mlp_bwd16.hip', 'mlp_bwd_f16x3.hip', 'normal_fit.hip', 'sds_elem.hip', 'group_norm.hip', 'f16x3_producers.hip', 'conv3x3.hip', 'gemm_f16x3.hip', 'attention.hip', 'transformer.hip', 'hashgrid.hip', 'hashgrid_fused.hip', 'skinny_gemm.hip',
            'sd_sample.hip', 'mcubes.hip', 'occupancy.hip', 'region.hip', 'distortion.hip', 'harmonic.hip', 'warp.hip', 'ssim.hip', 'components.hip', 'exemplar.hip', 'tsdf.hip', 'mesh_ops.hip', 'raster.hip', 'texture.hip', 'mesh_distance.hip',
-           'ray_depth.hip', 'depth_consistency.hip', 'mesh_raycast.hip', 'mesh_topology.hip', 'mesh_voxel.hip']
+           'ray_depth.hip', 'depth_consistency.hip', 'mesh_raycast.hip', 'mesh_topology.hip', 'mesh_voxel.hip', 'mesh_sdf.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=off', '-Wall',
          '-Wno-unused-function'] + EXTRA_FLAGS
 

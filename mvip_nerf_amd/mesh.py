@@ -18,6 +18,9 @@ load_ply() reads back what save_ply() wrote, bit for bit; how far two meshes lie
 cast_rays() / cast_views() / face_openness() / drop_interior() ask what a ray hits (csrc/mesh_raycast.hip): the first face along
 render_rays' own ray rows, frames without the rasteriser's near-plane drop, and the faces of interior shells that see nothing
 but mesh.
+signed_distance() / sdf_grid() / remesh() say on which side of the surface a point lies and how far (csrc/mesh_sdf.hip), on
+points or on a lattice, and extract the mesh again from that field: closed and evenly tessellated, optionally offset;
+margin_cells() is the metric margin of Region.from_mesh / OccupancyGrid.from_mesh.
 
 Conventions (shared with csrc/mcubes.hip and the test restatement tests/mc_numpy.py): grid [nx, ny, nz], z fastest; point
 (i, j, k) sits at bmin + (i, j, k) * (bmax - bmin) / (n - 1), in fp32 arithmetic; a corner is inside iff sigma >= threshold
@@ -820,6 +823,108 @@ def close_holes(mesh, max_edges=64):
     if normals is not None:
         normals = torch.cat([normals, ops.mesh_vertex_normals(verts, faces)[mesh.verts.shape[0]:]]).contiguous()
     return Mesh(verts, faces, normals, colors), n_capped, left
+
+
+# ---- signed distance (csrc/mesh_sdf.hip): which side of the surface, how far, and the mesh extracted again from that field ------
+SDF_DEFAULT_BAND_STEPS = 3.0
+REMESH_MIN_BAND_STEPS = 2.0
+
+
+def signed_distance(mesh, points, max_dist=None):
+    """(sdist [N] fp32, face [N] int32, point [N, 3] fp32) of points [N, 3] against the mesh (ops.mesh_signed_distance): the
+    distance to the closest point of the surface, negative inside a closed mesh with outward faces (marching_cubes', close_holes'
+    orientation); max_dist: points farther than it get face -1 and NaN.  On an open or inconsistently oriented mesh the sign is
+    that of the closest feature's pseudonormal and means what that mesh's orientation means: topology() says which it is."""
+    pts = torch.as_tensor(points, dtype=torch.float32).reshape(-1, 3).to(mesh.verts.device).contiguous()
+    return ops.mesh_signed_distance(pts, mesh.verts, mesh.faces, max_dist=max_dist)
+
+
+def _largest_step(bound_min, bound_max, resolution):
+    return float(max(ops.mesh_lattice(bound_min, bound_max, resolution)[1]))
+
+
+def sdf_grid(mesh, bound_min, bound_max, resolution, band=None):
+    """(sd [nx, ny, nz] fp32, valid [nx, ny, nz] bool): the signed distance of the mesh on the lattice of grid_axes(bound_min,
+    bound_max, resolution) within `band` of the surface (None: three times the largest lattice step); valid = within the band,
+    sd is NaN elsewhere.  One lattice-mode launch (ops.mesh_signed_distance_lattice): the lattice points are never written out,
+    and a point far from the surface costs the few cells it takes to know that."""
+    lo, hi = _bounds(bound_min, bound_max)
+    if band is None:
+        band = SDF_DEFAULT_BAND_STEPS * _largest_step(lo, hi, resolution)
+    sd, face = ops.mesh_signed_distance_lattice(mesh.verts, mesh.faces, lo, hi, resolution, max_dist=band)
+    return sd, face >= 0
+
+
+def remesh(mesh, resolution=256, offset=0.0, band=None, bound_min=None, bound_max=None):
+    """The level set sdist = offset of the mesh's signed distance, extracted again by marching cubes on `resolution` lattice
+    points per axis: a closed, evenly tessellated Mesh (no colours: colors_from_views / bake_texture give it some; normals from
+    its faces) in place of whatever drop_interior, keep_components and close_holes left -- centroid fans, slivers, sheets that
+    touch.  offset > 0 grows the shape, < 0 shrinks it.  The lattice handed to marching_cubes is band - sd where sd is known and
+    0 elsewhere, the threshold band - offset, with sdf_grid's valid lattice: "threshold > 0, inside is >=", as fuse_depths.
+    band None: three lattice steps; ValueError unless |offset| + 2 steps <= band (every corner of a cell the level set crosses
+    must lie within the band).  The default box is the vertex bounds grown by band.  The sign needs a closed, consistently
+    oriented input (topology()); on an open sheet the result is the sheet's two-sided band only where the pseudonormal sign
+    happens to flip, which is not a use of this function."""
+    res = (int(resolution),) * 3 if np.isscalar(resolution) else tuple(int(n) for n in resolution)
+    _check_axes(res)
+    offset = float(offset)
+    if not math.isfinite(offset):
+        raise ValueError(f'remesh: offset must be finite, got {offset}')
+    if int(mesh.verts.shape[0]) == 0 or int(mesh.faces.shape[0]) == 0:
+        raise ValueError('remesh: an empty mesh has no distance field')
+    if (bound_min is None) != (bound_max is None):
+        raise ValueError('remesh: bound_min and bound_max go together')
+    if bound_min is None:
+        vlo, vhi = (t.cpu().numpy().astype(np.float64) for t in (mesh.verts.amin(0), mesh.verts.amax(0)))
+        if band is None:                                      # band = 3 steps of the box grown by band: solve for band
+            if min(res) <= 2 * SDF_DEFAULT_BAND_STEPS + 1:
+                raise ValueError(f'remesh: resolution {res} leaves no room for a band of {SDF_DEFAULT_BAND_STEPS} steps on each side')
+            grow = max(SDF_DEFAULT_BAND_STEPS * (vhi[a] - vlo[a]) / (res[a] - 1 - 2 * SDF_DEFAULT_BAND_STEPS) for a in range(3))
+            grow = max(grow, 1e-6 * max(1.0, float(np.abs(np.concatenate([vlo, vhi])).max())))        # a flat mesh still gets a box
+        else:
+            grow = float(band)
+        if not (math.isfinite(grow) and grow > 0):
+            raise ValueError(f'remesh: band must be finite and > 0, got {band!r}')
+        bound_min, bound_max = vlo - grow, vhi + grow
+    lo, hi = _bounds(bound_min, bound_max)
+    step = _largest_step(lo, hi, res)
+    band = SDF_DEFAULT_BAND_STEPS * step if band is None else float(band)
+    if not (math.isfinite(band) and abs(offset) + REMESH_MIN_BAND_STEPS * step <= band):
+        raise ValueError(f'remesh: |offset| + {REMESH_MIN_BAND_STEPS:g} lattice steps = {abs(offset) + REMESH_MIN_BAND_STEPS * step:g} '
+                         f'must not exceed band = {band:g}')
+    sd, valid = sdf_grid(mesh, lo, hi, res, band)
+    g = torch.where(valid, band - sd, torch.zeros_like(sd)).contiguous()
+    verts, faces, _ = marching_cubes(g, band - offset, lo, hi, valid=valid.contiguous())
+    normals = ops.mesh_vertex_normals(verts, faces) if verts.shape[0] else verts.clone()
+    return Mesh(verts, faces, normals, None)
+
+
+def margin_cells(mesh, bmin, bmax, cells, margin):
+    """int32 words (the bit grid of `cells` cells on [bmin, bmax]) of the cells whose CENTRE lies within |margin| of the mesh's
+    surface: the metric margin of Region.from_mesh / OccupancyGrid.from_mesh.  One lattice-mode launch with max_dist = |margin|
+    on the fp32 centres fp32(bmin + w / 2) .. fp32(bmax - w / 2), w = (bmax - bmin) / cells in fp64, computed once here; in the
+    band <=> face >= 0; packed by ops.grid_pack.  ValueError for a margin that is not finite, and (the lattice needs two points
+    per axis) for an axis of one cell."""
+    from . import bitgrid
+    cells = bitgrid._cells(cells)
+    margin = float(margin)
+    if not math.isfinite(margin):
+        raise ValueError(f'margin must be finite, got {margin}')
+    if min(cells) < 2:
+        raise ValueError(f'a margin needs at least two cells per axis, got {cells}')
+    lo, hi = _bounds(bmin, bmax)
+    w = (hi.astype(np.float64) - lo.astype(np.float64)) / np.asarray(cells, np.float64)
+    first, last = (lo.astype(np.float64) + w / 2).astype(np.float32), (hi.astype(np.float64) - w / 2).astype(np.float32)
+    _, face = ops.mesh_signed_distance_lattice(mesh.verts, mesh.faces, first, last, cells, max_dist=abs(margin))
+    return ops.grid_pack((face >= 0).to(torch.float32), 0.5)
+
+
+def apply_margin(words, mesh, bmin, bmax, cells, margin):
+    """words with the cells of margin_cells set (margin > 0) or cleared (margin < 0); margin None or 0: words as they are."""
+    if margin is None or float(margin) == 0.0:
+        return words
+    m = margin_cells(mesh, bmin, bmax, cells, margin)
+    return (words | m) if float(margin) > 0 else (words & ~m)
 
 
 Texture = collections.namedtuple('Texture', ['image', 'uv', 'seen', 'texels'])

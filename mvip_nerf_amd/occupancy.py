@@ -78,17 +78,20 @@ class OccupancyGrid(BitGrid):
         return cls(lo, hi, cells, words)
 
     @classmethod
-    def from_mesh(cls, mesh, bmin, bmax, cells=128, solid=True, dilate=1):
+    def from_mesh(cls, mesh, bmin, bmax, cells=128, solid=True, dilate=1, margin=None):
         """The cells of a mesh.Mesh on the GPU as occupied cells (mesh.voxelize, csrc/mesh_voxel.hip), then `dilate` rounds
         of dilation: the cells the faces touch, and with solid=True the cells inside as well (column parity, the majority of
         three axes).  Like keep_components, and unlike from_model, this grid is NOT conservative for the field: a render with
         it shows the scene ONLY where the mesh is -- whatever the cleaned mesh no longer has (floaters, dropped interior,
-        deselected components) is gone from the frame, not merely skipped, so the frame differs from the unskipped render."""
+        deselected components) is gone from the frame, not merely skipped, so the frame differs from the unskipped render.
+        margin (scene units; None: no such step), applied after the voxelisation and before the dilation: > 0 also sets the
+        cells whose centre lies within `margin` of the surface, < 0 clears them (mesh.margin_cells, csrc/mesh_sdf.hip)."""
         cells = _cells(cells)
         rounds = _count('dilate', dilate, 0, MAX_CELLS_PER_AXIS)
         from .mesh import voxelize                                   # (the argument shadows the module here)
+        from .mesh import apply_margin
         grid, _ = voxelize(mesh, bmin, bmax, cells, mode='both' if solid else 'surface')
-        words = grid.words
+        words = apply_margin(grid.words, mesh, grid.bmin, grid.bmax, cells, margin)
         for _ in range(rounds):
             words = ops.occupancy_dilate(words, cells)
         return cls(grid.bmin, grid.bmax, cells, words)

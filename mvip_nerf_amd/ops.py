@@ -3191,6 +3191,155 @@ def mesh_sample_faces(verts, faces, k):
     return pts, fos, w
 
 
+# signed mesh distance: pseudonormal sign on the closest point, for points or a lattice (beyond the reference, csrc/mesh_sdf.hip) ---
+# The definition is csrc/mesh_sdf.hip's and tests/mesh_sdf_numpy.py's.  There is no CPU path.
+
+def mesh_vertex_pseudonormals(verts, faces):
+    """P [V, 3] fp64 of an indexed mesh: per vertex the sum over its corner list, in order, of (the angle of the corner) x (the
+    unit normal of its face), in fp64, unnormalised; zeros for a vertex without faces (csrc/mesh_sdf.hip).  The sign of
+    mesh_signed_distance at a query whose closest point is a vertex.  ValueError as mesh_corner_table."""
+    v, f = _mesh_operands('mesh_vertex_pseudonormals', verts, faces)
+    V, F = int(v.shape[0]), int(f.shape[0])
+    offsets, corners = mesh_corner_table(f, V)
+    P = torch.empty((V, 3), device=v.device, dtype=torch.float64)
+    if V:
+        call('mvip_mesh_vertex_pseudonormals', ptr(v), ptr(f, _I32) if F else ptr(None), V, F, ptr(offsets, _I32),
+             ptr(corners, _I32) if F else ptr(None), ptr(P, torch.float64), stream())
+    return P
+
+
+def _band(what, max_dist):
+    if max_dist is None:
+        return float('inf')
+    B = float(max_dist)
+    if not B >= 0.0:
+        raise ValueError(f'{what}: max_dist must be None or a number >= 0, got {max_dist!r}')
+    return B
+
+
+def _sdf_mesh(what, verts, faces, grid, twin, pseudonormals):
+    """The mesh operands of mvip_mesh_signed_distance, checked; whatever is not given is built here."""
+    v, f = _mesh_operands(what, verts, faces)
+    V, F = int(v.shape[0]), int(f.shape[0])
+    if F == 0 or V == 0:
+        raise ValueError(f'{what}: a mesh of {F} faces and {V} vertices has no closest point')
+    if grid is None:
+        grid = mesh_face_grid(v, f)
+    elif not isinstance(grid, FaceGrid) or not grid.matches(v, f):
+        raise ValueError(f'{what}: grid must be the mesh_face_grid of these verts and faces')
+    for name, t, dtype, shape in (('twin', twin, _I32, (3 * F,)), ('pseudonormals', pseudonormals, torch.float64, (V, 3))):
+        if t is None:
+            continue
+        if not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != shape:
+            raise ValueError(f'{what}: {name} must be a {dtype} tensor of shape {shape}, got '
+                             f'{(t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__}')
+        if t.device != v.device or not t.is_contiguous():
+            raise ValueError(f'{what}: {name} must be contiguous and on {v.device}')
+    twin = mesh_edge_table(f, V).twin if twin is None else twin.detach()
+    P = mesh_vertex_pseudonormals(v, f) if pseudonormals is None else pseudonormals.detach()
+    return v, f, grid, twin, P
+
+
+def _signed_distance(p, lattice, N, v, f, grid, twin, P, B, want_point, want_feature, want_stats=False):
+    import ctypes
+    V, F = int(v.shape[0]), int(f.shape[0])
+    dev = v.device
+    sdist = torch.empty(N, device=dev, dtype=_F32)
+    face = torch.empty(N, device=dev, dtype=_I32)
+    point = torch.empty((N, 3), device=dev, dtype=_F32) if want_point else None
+    feature = torch.empty(N, device=dev, dtype=_I32) if want_feature else None
+    stats = torch.empty(2, device=dev, dtype=torch.int64) if want_stats else None
+    none = ptr(None)
+    cbox = (ctypes.c_float * 6)(*[float(x) for x in grid.box])
+    ccells = (ctypes.c_int * 3)(*grid.cells)
+    if lattice is None:
+        clo = ch = ccounts = None
+    else:
+        clo, ch = (ctypes.c_float * 3)(*[float(x) for x in lattice[0]]), (ctypes.c_float * 3)(*[float(x) for x in lattice[1]])
+        ccounts = (ctypes.c_int * 3)(*lattice[2])
+    call('mvip_mesh_signed_distance', ptr(p) if p is not None and N else none, clo, ch, ccounts, N, ptr(v), ptr(f, _I32), V, F, cbox,
+         ccells, ptr(grid.cell_offsets, _I32), ptr(grid.cell_faces, _I32) if grid.n_pairs else none, grid.n_pairs, ptr(twin, _I32),
+         ptr(P, torch.float64), B, ptr(sdist) if N else none, ptr(face, _I32) if N else none,
+         ptr(point) if want_point and N else none, ptr(feature, _I32) if want_feature and N else none,
+         ptr(stats, torch.int64) if want_stats else none, stream())
+    return sdist, face, point, feature, stats
+
+
+def mesh_signed_distance(points, verts, faces, grid=None, twin=None, pseudonormals=None, max_dist=None, return_feature=False,
+                         return_stats=False):
+    """The signed distance of each of points [N, 3] fp32 to the mesh (verts [V, 3] fp32, faces [F, 3] int32), all on the GPU:
+    (sdist [N] fp32, face [N] int32, point [N, 3] fp32), with return_feature=True also feature [N] int32.  face, point and
+    |sdist| are mesh_closest_point's; the sign is that of n . (p - q) with n the angle-weighted pseudonormal of the closest
+    feature (csrc/mesh_sdf.hip, tests/mesh_sdf_numpy.py): the face normal, the sum of the two unit normals at an edge (feature
+    1..3), the angle-weighted sum at a vertex (4..6).  Negative inside a closed mesh whose faces are counter-clockwise seen from
+    outside; defined, by the same rule, on any mesh (mesh.topology says what the mesh is).  max_dist: queries farther than it
+    get face -1 and NaN, as queries with a NaN or infinite coordinate do; the rest are unchanged by it.  grid / twin /
+    pseudonormals: those of mesh_face_grid / mesh_edge_table / mesh_vertex_pseudonormals for these tensors (None: built here).
+    A twin or pseudonormals that is given is checked for dtype, shape and device only and otherwise TRUSTED to be of this mesh:
+    one of another mesh gives wrong signs (never an access out of range: the kernel bounds every index it reads from them).
+    return_stats=True appends mesh_closest_point's [2] int64 counters (a counting variant of the kernel).
+    ValueError as mesh_closest_point, and for max_dist < 0 or NaN.  Detached."""
+    what = 'mesh_signed_distance'
+    if not torch.is_tensor(points):
+        raise ValueError(f'{what}: points must be a tensor on the GPU, got {type(points).__name__}')
+    if points.dtype != _F32:
+        raise ValueError(f'{what}: points must be {_F32}, got {points.dtype}')
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f'{what}: points must be [N, 3], got {tuple(points.shape)}')
+    p = points.detach()
+    if not p.is_cuda:
+        raise ValueError(f'{what}: tensors on the GPU expected (the HIP path has no CPU path)')
+    if not p.is_contiguous():
+        raise ValueError(f'{what}: every operand must be contiguous')
+    N = int(p.shape[0])
+    if 3 * N > 2 ** 31 - 1:
+        raise ValueError(f'{what}: {N} points exceed int32 indices')
+    B = _band(what, max_dist)
+    if torch.is_tensor(verts) and p.device != verts.device:
+        raise ValueError(f'{what}: tensors on one device expected, got {sorted({str(verts.device), str(p.device)})}')
+    v, f, grid, twin, P = _sdf_mesh(what, verts, faces, grid, twin, pseudonormals)
+    sdist, face, point, feature, stats = _signed_distance(p, None, N, v, f, grid, twin, P, B, True, return_feature, return_stats)
+    out = (sdist, face, point, feature) if return_feature else (sdist, face, point)
+    return out + (stats,) if return_stats else out
+
+
+def mesh_lattice(bound_min, bound_max, resolution):
+    """(lo fp32 [3], h fp32 [3], counts (nx, ny, nz)) of the lattice of mesh.grid_axes: point i of an axis is fp32(fp32(i) h) + lo,
+    h = (hi - lo) / fp32(n - 1) in fp32.  Host code.  ValueError for a count below 2, non-finite bounds, a step that is not > 0,
+    more than 2^31 - 1 points."""
+    import numpy as np
+    what = 'mesh_signed_distance_lattice'
+    lo, hi = np.asarray(bound_min, np.float32).reshape(-1), np.asarray(bound_max, np.float32).reshape(-1)
+    if lo.shape != (3,) or hi.shape != (3,) or not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi))):
+        raise ValueError(f'{what}: bound_min / bound_max must be three finite numbers each')
+    counts = (int(resolution),) * 3 if np.isscalar(resolution) else tuple(int(n) for n in resolution)
+    if len(counts) != 3 or min(counts) < 2:
+        raise ValueError(f'{what}: resolution must be one or three counts >= 2, got {resolution!r}')
+    if counts[0] * counts[1] * counts[2] > 2 ** 31 - 1:
+        raise ValueError(f'{what}: {counts} lattice points exceed int32 indices')
+    with np.errstate(over='ignore', invalid='ignore'):
+        h = np.asarray([(hi[a] - lo[a]) / np.float32(counts[a] - 1) for a in range(3)], np.float32)
+    if not (np.all(np.isfinite(h)) and np.all(h > 0)):
+        raise ValueError(f'{what}: the box {lo.tolist()} .. {hi.tolist()} has no finite step > 0 on {counts} points')
+    return lo, h, counts
+
+
+def mesh_signed_distance_lattice(verts, faces, bound_min, bound_max, resolution, max_dist=None, grid=None, twin=None,
+                                 pseudonormals=None, return_stats=False):
+    """mesh_signed_distance on the lattice of mesh.grid_axes(bound_min, bound_max, resolution) without the [N, 3] tensor of its
+    points (the kernel generates them, bit for bit those of grid_axes): (sdist [nx, ny, nz] fp32, face [nx, ny, nz] int32).
+    With max_dist the walk of a far point ends as soon as nothing within max_dist can remain: a narrow band of a large lattice
+    costs little more than its in-band points.  return_stats=True appends the [2] int64 counters.  ValueError as mesh_signed_distance and mesh_lattice."""
+    what = 'mesh_signed_distance_lattice'
+    lattice = mesh_lattice(bound_min, bound_max, resolution)
+    B = _band(what, max_dist)
+    v, f, grid, twin, P = _sdf_mesh(what, verts, faces, grid, twin, pseudonormals)
+    counts = lattice[2]
+    sdist, face, _, _, stats = _signed_distance(None, lattice, counts[0] * counts[1] * counts[2], v, f, grid, twin, P, B, False, False,
+                                                return_stats)
+    return (sdist.view(counts), face.view(counts), stats) if return_stats else (sdist.view(counts), face.view(counts))
+
+
 # mesh ray casting: first hit, occlusion, face openness on the face grid (beyond the reference, csrc/mesh_raycast.hip) ---------------
 # The definition is csrc/mesh_raycast.hip's and tests/mesh_raycast_numpy.py's.  There is no CPU path.
 

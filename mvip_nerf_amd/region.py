@@ -116,13 +116,17 @@ class Region(BitGrid):
         return r.dilate(rounds)
 
     @classmethod
-    def from_mesh(cls, mesh, bmin=None, bmax=None, cells=64, solid=True, dilate=1):
+    def from_mesh(cls, mesh, bmin=None, bmax=None, cells=64, solid=True, dilate=1, margin=None):
         """The cells of a mesh (mesh.voxelize, csrc/mesh_voxel.hip), then `dilate` rounds of dilation: with solid=True the
         cells the faces touch and the cells inside (column parity, the majority of three axes: a hole in the mesh leaks
         nothing beyond the missing faces' own cells), with solid=False the surface cells only.  mesh: a mesh.Mesh on the
         GPU, for instance one component picked by mesh.keep_components(containing=...).  With no box given: default_box over
         the finite vertices, as from_points.  The region renders into every view as an occlusion-aware mask (propagate_masks)
-        and carve() cuts it out of the scene."""
+        and carve() cuts it out of the scene.
+        margin (scene units; None: no such step), applied after the voxelisation and before the dilation: > 0 also sets every
+        cell whose centre lies within `margin` of the surface -- the halo and the contact shadow round an object, by a
+        distance and not by whole cells; < 0 clears those cells, which peels a solid region by |margin| (mesh.margin_cells,
+        csrc/mesh_sdf.hip).  A box derived here is not grown by the margin: give one that holds it."""
         cells = _cells(cells)
         rounds = _count('dilate', dilate, 0, MAX_CELLS_PER_AXIS)
         if (bmin is None) != (bmax is None):
@@ -134,8 +138,10 @@ class Region(BitGrid):
                 raise ValueError('no finite vertex: the box cannot be derived from the mesh')
             bmin, bmax = default_box(finite.min(0).values.cpu().numpy(), finite.max(0).values.cpu().numpy(), cells, rounds)
         from .mesh import voxelize                                   # (the argument shadows the module here)
+        from .mesh import apply_margin
         grid, _ = voxelize(mesh, bmin, bmax, cells, mode='both' if solid else 'surface')
-        return cls(grid.bmin, grid.bmax, cells, grid.words).dilate(rounds)
+        words = apply_margin(grid.words, mesh, grid.bmin, grid.bmax, cells, margin)
+        return cls(grid.bmin, grid.bmax, cells, words).dilate(rounds)
 
     @classmethod
     def from_masks(cls, render_kwargs, hwf, poses, masks, near, far, bmin=None, bmax=None, cells=64, min_weight=None,

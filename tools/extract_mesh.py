@@ -37,7 +37,10 @@ shells go, exterior surface stays whether or not a camera saw it.  It needs no c
 caps every closed boundary loop of at most N edges with a fan round its centroid (mesh.close_holes): right for the small
 cuts those options leave, wrong for large or bent holes, hence the limit.  --report-topology prints `topology: {JSON}` of the
 mesh that is written (mesh.topology: components, boundary / non-manifold / inconsistent edges, Euler characteristic, genus,
-loops).  They come after all other clean-up, in this order, and before --texture.  Without the flags every output is what
+loops).  --remesh RES [--remesh-offset D] then extracts the mesh again from its own signed distance field at RES lattice points
+per axis, at the level D (mesh.remesh, csrc/mesh_sdf.hip): a closed, evenly tessellated surface in place of fans and slivers;
+it needs a closed, consistently oriented mesh (--report-topology says) and drops the colours.  They come after all other
+clean-up, in this order, and before --texture.  Without the flags every output is what
 it was.
 
 --report-error prints what the clean-up cost: the distance report of the finished mesh (after --smooth, --simplify and
@@ -168,7 +171,8 @@ def drop_unseen(a, m, hwf, poses):
 
 
 def mesh_topology_options(a, m):
-    """--mesh-largest / --mesh-min-faces, --close-holes, --report-topology on the finished Mesh m, in this order: (mesh, seconds)."""
+    """--mesh-largest / --mesh-min-faces, --close-holes, --remesh, --report-topology on the finished Mesh m, in this order: (mesh,
+    seconds)."""
     t = 0.0
     if a.mesh_largest is not None or a.mesh_min_faces is not None:
         out, dt = _timed(lambda: mesh.keep_components(m, largest=a.mesh_largest, min_faces=a.mesh_min_faces))
@@ -179,6 +183,11 @@ def mesh_topology_options(a, m):
         (out, capped, left), dt = _timed(lambda: mesh.close_holes(m, max_edges=a.close_holes))
         print(f'holes of at most {a.close_holes} edges: {capped} capped, {left} loops left open, {m.faces.shape[0]} -> '
               f'{out.faces.shape[0]} triangles  ({dt * 1e3:.1f} ms)')
+        m, t = out, t + dt
+    if a.remesh:
+        out, dt = _timed(lambda: mesh.remesh(m, resolution=a.remesh, offset=a.remesh_offset))
+        print(f'remeshed at {a.remesh} points per axis, offset {a.remesh_offset:g}: {m.faces.shape[0]} triangles, {m.verts.shape[0]} '
+              f'vertices -> {out.faces.shape[0]} triangles, {out.verts.shape[0]} vertices, colours dropped  ({dt * 1e3:.1f} ms)')
         m, t = out, t + dt
     if a.report_topology:
         rep = mesh.topology(m)
@@ -327,6 +336,9 @@ def main(argv=None):
     ap.add_argument('--mesh-min-faces', type=int, default=None, metavar='N', help='drop mesh components below N faces')
     ap.add_argument('--close-holes', type=int, default=0, metavar='N',
                     help='cap the closed boundary loops of at most N edges with a centroid fan (0: off)')
+    ap.add_argument('--remesh', type=int, default=0, metavar='RES',
+                    help='extract the mesh again from its own signed distance field at RES lattice points per axis (0: off)')
+    ap.add_argument('--remesh-offset', type=float, default=0.0, metavar='D', help='--remesh: the level, > 0 grows the shape')
     ap.add_argument('--report-topology', action='store_true', help='print the topology report of the mesh that is written')
     ap.add_argument('--report-error', action='store_true',
                     help='print the distance report of the finished mesh against the mesh as first extracted')
@@ -356,6 +368,10 @@ def main(argv=None):
         ap.error('--drop-interior: 1..255 directions')
     if (a.mesh_largest is not None and a.mesh_largest < 1) or (a.mesh_min_faces is not None and a.mesh_min_faces < 1):
         ap.error('--mesh-largest and --mesh-min-faces must be >= 1')
+    if a.remesh != 0 and not 8 <= a.remesh <= mesh.MAX_POINTS_PER_AXIS:
+        ap.error(f'--remesh: 8..{mesh.MAX_POINTS_PER_AXIS} lattice points per axis')
+    if a.remesh_offset != 0.0 and not a.remesh:
+        ap.error('--remesh-offset belongs to --remesh')
     if a.close_holes != 0 and a.close_holes < 3:
         ap.error('--close-holes: at least 3 edges (0: off)')
     if not 0 <= a.texture <= 32 or (a.texture and not a.out.endswith('.obj')):

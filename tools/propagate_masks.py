@@ -14,7 +14,8 @@ propagated; the JSON then carries the cell and component counts before the cut a
 
 --mesh A.ply builds the region from a mesh instead of from annotated views (Region.from_mesh, csrc/mesh_voxel.hip: the cells
 the mesh touches and the cells inside it; --cells and --dilate as for the lifted region): the whole mesh, or with --mesh-point
-X,Y,Z the connected component whose surface is closest to that point (mesh.keep_components).  No view is annotated: the IoU is
+X,Y,Z the connected component whose surface is closest to that point (mesh.keep_components); --mesh-margin D also masks the
+cells whose centre lies within D scene units of the surface (the halo and contact shadow round an object; csrc/mesh_sdf.hip).  No view is annotated: the IoU is
 reported over every view that has a dataset mask, there is no copy baseline, and the set's folder is DIR/mesh/.
 
 Per set, into DIR/views_<set>/: label/NNNNNN.png (0 / 255, one per view, the layout load_llff._load_data reads; with
@@ -91,7 +92,7 @@ def region_from_mesh(a, device):
         if len(point) != 3:
             raise SystemExit('--mesh-point: X,Y,Z')
         m = mesh.keep_components(m, containing=torch.tensor([point]))
-    return Region.from_mesh(m, cells=a.cells, dilate=a.dilate)
+    return Region.from_mesh(m, cells=a.cells, dilate=a.dilate, margin=a.mesh_margin)
 
 
 def main(argv=None):
@@ -110,12 +111,14 @@ def main(argv=None):
     ap.add_argument('--keep-largest', type=int, default=None, metavar='K', help='keep the K largest components of the region')
     ap.add_argument('--mesh', metavar='PLY', help='build the region from this mesh instead of from annotated views')
     ap.add_argument('--mesh-point', metavar='X,Y,Z', help='--mesh: only the component closest to this point')
+    ap.add_argument('--mesh-margin', type=float, default=None, metavar='D',
+                    help='--mesh: also mask the cells whose centre lies within D scene units of the mesh (D < 0: unmask them)')
     ap.add_argument('--carve-preview', type=int, default=None, metavar='VIEW')
     a = ap.parse_args(argv)
     if a.fixture == bool(a.checkpoint) or bool(a.checkpoint) != bool(a.datadir):
         ap.error('either --fixture, or --checkpoint with --datadir')
-    if (a.mesh_point and not a.mesh) or (a.mesh and a.views):
-        ap.error('--mesh-point belongs to --mesh; --mesh and --views exclude each other')
+    if ((a.mesh_point or a.mesh_margin is not None) and not a.mesh) or (a.mesh and a.views):
+        ap.error('--mesh-point and --mesh-margin belong to --mesh; --mesh and --views exclude each other')
     dev = torch.device('cuda', 0)
 
     def timed(fn):
@@ -168,7 +171,7 @@ def main(argv=None):
                'seconds_lift': t_lift, 'seconds_propagate_all_views': t_prop}
         rec.update(lifted or {})
         if spec is None:
-            rec.update(mesh=a.mesh, mesh_point=a.mesh_point)
+            rec.update(mesh=a.mesh, mesh_point=a.mesh_point, mesh_margin=a.mesh_margin)
         if a.carve_preview is not None:
             with torch.no_grad():
                 kw = dict(te, near=near, far=far)
